@@ -12,8 +12,13 @@ Also reported on the same JSON line:
   roofline      the homography-warp kernel (getcost_quad_kernel, launched stage_iters[1]=4 times per
                 step): algorithmic bytes per launch (SURVEY section 8d formula) / mean launch
                 duration from HIP events recorded on the launch stream inside the timed region
-  cpu_baseline  oracle/diffmvs_oracle.py (CPU restatement pinned to the reference) timed on this
-                box's host cores on a bounded sample of the same workload (rank 0, N=1 only)
+  cpu_baseline  (--full) oracle/diffmvs_oracle.py (CPU restatement pinned to the reference) timed on
+                this box's host cores on a bounded sample of the same workload (rank 0, N=1 only)
+
+A plain run sets up, warms up, times exactly --steps steps, writes the last step's outputs if
+--dump-outputs is given, and prints the line.  --full adds the side measurements that take steps
+or runs of their own (conv2d per-launch table, batch sweep, ceiling probe, scene geometry, CPU
+baseline, per-sample scene comparison, training-step backward rooflines).
 """
 import argparse
 import json
@@ -271,15 +276,46 @@ def spawn_ranks(n):
 
 
 def timed_steps(step, steps, warmup, barrier):
-    """W untimed + exactly K timed steps bracketed by barrier + device sync on both sides -> elapsed seconds"""
+    """W untimed + exactly K timed steps bracketed by barrier + device sync on both sides -> (elapsed seconds, what the last step returned)"""
     for _ in range(warmup):
-        step()
+        out = step()
     barrier()
     t0 = time.perf_counter()
     for _ in range(steps):
-        step()
+        out = step()
     barrier()
-    return time.perf_counter() - t0
+    return time.perf_counter() - t0, out
+
+
+DUMP_BUDGET_BYTES = 60 * 10 ** 6        # --dump-outputs stays under 64 MB
+
+
+def dump_outputs(arrays, directory, batch):
+    """--dump-outputs: the tensors the timed path returned in its last step (a dict of tensors and lists of tensors) -> directory/<name>.npy,
+    float64 kept, everything else as float32; a list's entries are <name>_<i>.  When the whole would exceed DUMP_BUDGET_BYTES, the arrays
+    whose leading dimension is the batch are cut down to one fixed, seeded sample of batch items (the same for every array and every run).
+    Returns what the line records about the files."""
+    import numpy as np
+    flat = {}
+    for k, v in arrays.items():
+        if torch.is_tensor(v):
+            flat[k] = v
+        elif isinstance(v, (list, tuple)):
+            flat.update({f"{k}_{i}": t for i, t in enumerate(v) if torch.is_tensor(t)})
+    nbytes = lambda t: t.numel() * (8 if t.dtype == torch.float64 else 4)  # noqa: E731
+    batched = {n for n, t in flat.items() if t.dim() > 0 and t.shape[0] == batch}
+    fixed = sum(nbytes(t) for n, t in flat.items() if n not in batched)
+    per_item = sum(nbytes(flat[n]) for n in batched) / batch if batched else 0.0
+    keep = batch if fixed + per_item * batch <= DUMP_BUDGET_BYTES else max(1, int((DUMP_BUDGET_BYTES - fixed) // per_item))
+    items = torch.randperm(batch, generator=torch.Generator().manual_seed(0))[:keep].sort().values
+    os.makedirs(directory, exist_ok=True)
+    for n, t in flat.items():
+        t = t.detach()
+        if n in batched and keep < batch:
+            t = t.index_select(0, items.to(t.device))
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        np.save(os.path.join(directory, n + ".npy"), t.cpu().numpy())
+    return {"dir": directory, "arrays": sorted(flat), "batch_items": "all" if keep == batch else items.tolist()}
 
 
 def stub_main(a):
@@ -316,9 +352,11 @@ def stub_main(a):
             bucket.mul_(1.0 / world)
         return y
 
-    elapsed = timed_steps(step, a.steps, a.warmup, (lambda: td.barrier()) if td else (lambda: None))
+    elapsed, out = timed_steps(step, a.steps, a.warmup, (lambda: td.barrier()) if td else (lambda: None))
     whole = shard.barrier_and_max(elapsed)
     total_units = shard.total_items(units_per_step) if kind in ("cfg5", "scene") else units_per_step * world
+    if a.dump_outputs and rank == 0:
+        extra["dumped_outputs"] = dump_outputs({"stub_output": out}, a.dump_outputs, out.shape[0])
     if bucket is not None:
         extra["allreduce_ms_per_step"] = round(1e3 * sum(ar_s[-a.steps:]) / max(1, len(ar_s[-a.steps:])), 4) if ar_s else None
         # every rank holds the same averaged bucket after each step (the mean of 1..world stays fixed under repeated averaging)
@@ -374,36 +412,40 @@ def train_main(a):
             td.barrier()
         torch.cuda.synchronize()
 
-    last = {}
-
     def step():
-        last["loss"] = tr.train_sample(sample)[0]
+        return tr.train_sample(sample)
 
     for _ in range(a.warmup):
         step()
     tr.allreduce_events.clear()
-    elapsed = timed_steps(step, a.steps, 0, barrier)
+    elapsed, last = timed_steps(step, a.steps, 0, barrier)
     elapsed = shard.barrier_and_max(elapsed, dev)
     ar_ms = [s_.elapsed_time(e_) for s_, e_ in tr.allreduce_events]
-    # one extra, untimed step with an event pair around the backward's two dominant kernel families (kept out of the timed region)
-    from diffmvs_amd.ops import Ops
-    ops = Ops.for_device(dev)
-    ops.timers = {"dmvs_getcost_bwd_f32": [], "dmvs_conv2d_wgrad_f32": []}
-    step()
-    torch.cuda.synchronize()
-    tm, ops.timers = ops.timers, None
-    gb_ms = [s_.elapsed_time(e_) for s_, e_ in tm["dmvs_getcost_bwd_f32"]]
-    wg_ms = [s_.elapsed_time(e_) for s_, e_ in tm["dmvs_conv2d_wgrad_f32"]]
-    gb_bytes, wg_flops = sum(tm.get("_getcost_bwd_bytes", [])), sum(tm.get("_wgrad_flops", []))
-    roof = {"roofline_getcost_bwd": {"kernel": "getcost_bwd_kernel<*> (gradient scatter into the source features, hardware fp32 atomics)", "bound": "hbm",
-                                     "achieved": round(gb_bytes / (sum(gb_ms) * 1e-3) / 1e9, 2) if gb_ms else None, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                     "frac": round(gb_bytes / (sum(gb_ms) * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if gb_ms else None,
-                                     "launches": len(gb_ms), "ms_per_step": round(sum(gb_ms), 3),
-                                     "note": "bound in practice by the L2's fp32 atomic rate (one atomic per tap and channel), not by HBM: DESIGN.md 3.2"},
-            "roofline_conv2d_wgrad": {"kernel": "conv2d_wgrad_kernel<*> (all weight-gradient launches of the step)", "bound": "mfma",
-                                      "achieved": round(wg_flops / (sum(wg_ms) * 1e-3) / 1e12, 2) if wg_ms else None, "peak": FP32_MFMA_PEAK_TFS, "unit": "TFLOP/s",
-                                      "frac": round(wg_flops / (sum(wg_ms) * 1e-3) / 1e12 / FP32_MFMA_PEAK_TFS, 4) if wg_ms else None,
-                                      "launches": len(wg_ms), "ms_per_step": round(sum(wg_ms), 3)}}
+    loss, _, gnorm, out = last
+    dumped = dump_outputs({"loss": loss.reshape(1), "grad_norm": gnorm.reshape(1), "parameters": tr.flat.data, **out}, a.dump_outputs, B) \
+        if (a.dump_outputs and rank == 0) else None
+    del last, out
+    roof = {"roofline_getcost_bwd": None, "roofline_conv2d_wgrad": None}
+    if a.full:
+        # one extra, untimed step with an event pair around the backward's two dominant kernel families (kept out of the timed region)
+        from diffmvs_amd.ops import Ops
+        ops = Ops.for_device(dev)
+        ops.timers = {"dmvs_getcost_bwd_f32": [], "dmvs_conv2d_wgrad_f32": []}
+        step()
+        torch.cuda.synchronize()
+        tm, ops.timers = ops.timers, None
+        gb_ms = [s_.elapsed_time(e_) for s_, e_ in tm["dmvs_getcost_bwd_f32"]]
+        wg_ms = [s_.elapsed_time(e_) for s_, e_ in tm["dmvs_conv2d_wgrad_f32"]]
+        gb_bytes, wg_flops = sum(tm.get("_getcost_bwd_bytes", [])), sum(tm.get("_wgrad_flops", []))
+        roof = {"roofline_getcost_bwd": {"kernel": "getcost_bwd_kernel<*> (gradient scatter into the source features, hardware fp32 atomics)", "bound": "hbm",
+                                         "achieved": round(gb_bytes / (sum(gb_ms) * 1e-3) / 1e9, 2) if gb_ms else None, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                         "frac": round(gb_bytes / (sum(gb_ms) * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if gb_ms else None,
+                                         "launches": len(gb_ms), "ms_per_step": round(sum(gb_ms), 3),
+                                         "note": "bound in practice by the L2's fp32 atomic rate (one atomic per tap and channel), not by HBM: DESIGN.md 3.2"},
+                "roofline_conv2d_wgrad": {"kernel": "conv2d_wgrad_kernel<*> (all weight-gradient launches of the step)", "bound": "mfma",
+                                          "achieved": round(wg_flops / (sum(wg_ms) * 1e-3) / 1e12, 2) if wg_ms else None, "peak": FP32_MFMA_PEAK_TFS, "unit": "TFLOP/s",
+                                          "frac": round(wg_flops / (sum(wg_ms) * 1e-3) / 1e12 / FP32_MFMA_PEAK_TFS, 4) if wg_ms else None,
+                                          "launches": len(wg_ms), "ms_per_step": round(sum(wg_ms), 3)}}
     if rank == 0:
         print(json.dumps({
             "metric": "training samples/sec (CasDiffMVS 768x576, 9 views)", "value": round(B * world * a.steps / elapsed, 3), "unit": "samples/s",
@@ -414,8 +456,8 @@ def train_main(a):
                        "batch_per_gpu": B, "parallelism": f"data parallel x{world}: one all-reduce (SUM) of the {tr.flat.numel * 4 / 1e6:.2f} MB flat fp32 gradient bucket per step",
                        "weights": "seeded random init"},
             "allreduce_ms_per_step": round(sum(ar_ms) / max(1, len(ar_ms)), 4) if ar_ms else None,
-            "allreduce_bytes": tr.flat.numel * 4, "loss": float(last["loss"]), **roof,
-            "max_mem_GB": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)}), flush=True)
+            "allreduce_bytes": tr.flat.numel * 4, "loss": float(loss), **roof,
+            "max_mem_GB": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2), "full": a.full, "dumped_outputs": dumped}), flush=True)
     if td:
         td.destroy_process_group()
 
@@ -469,11 +511,15 @@ def scene_main(a):
     def step_per_sample():
         return model(per_sample_imgs, proj_d, dv_d)
 
-    with torch.no_grad():
-        elapsed = timed_steps(step, a.steps, a.warmup, barrier)
-        elapsed = shard.barrier_and_max(elapsed, dev)
-        ps = timed_steps(step_per_sample, max(2, a.steps // 4), 1, barrier) / max(2, a.steps // 4)
     maps = NV * k
+    with torch.no_grad():
+        elapsed, out = timed_steps(step, a.steps, a.warmup, barrier)
+        elapsed = shard.barrier_and_max(elapsed, dev)
+        dumped = dump_outputs(out, a.dump_outputs, maps) if (a.dump_outputs and rank == 0) else None
+        del out
+        ps = None
+        if a.full:      # the same scenes through the per-sample forward: steps of their own
+            ps = timed_steps(step_per_sample, max(2, a.steps // 4), 1, barrier)[0] / max(2, a.steps // 4)
     if rank == 0:
         print(json.dumps({
             "metric": f"depth-maps/sec ({W}x{H}, {S} src views), scene mode", "value": round(maps * a.steps * world / elapsed, 3), "unit": "depth-maps/s",
@@ -486,9 +532,10 @@ def scene_main(a):
                        "images_through_featurenet_per_step_per_sample_mode": maps * (S + 1),
                        "parallelism": f"scene sharding x{world}, no collective", "weights": "seeded random init"},
             "per_sample": {"ms_per_step": round(ps * 1e3, 4), "depth_maps_per_s": round(maps / ps, 3),
-                           "note": "the same scenes, FeatureNet on all V images of every reference view (reference test.py:92-127; the headline's order of work)"},
-            "speedup_vs_per_sample": round(ps / (elapsed / a.steps), 4),
-            "max_mem_GB": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)}), flush=True)
+                           "note": "the same scenes, FeatureNet on all V images of every reference view (reference test.py:92-127; the headline's order of work)"}
+                          if ps else None,
+            "speedup_vs_per_sample": round(ps / (elapsed / a.steps), 4) if ps else None,
+            "max_mem_GB": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2), "full": a.full, "dumped_outputs": dumped}), flush=True)
     if td:
         td.destroy_process_group()
 
@@ -518,16 +565,30 @@ def main():
     ap.add_argument("--scenes-per-step", type=int, default=2)
     ap.add_argument("--scene-views", type=int, default=49)
     ap.add_argument("--graphs", action="store_true", help="run the timed steps through the captured HIP graph of the forward")
-    ap.add_argument("--no-batch-sweep", action="store_true")
-    ap.add_argument("--conv-table", action="store_true", help="print the per-shape table of the step's conv2d launches to stderr")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-probe", action="store_true", help="skip the GetCost ceiling-probe / random-line-gather legs (untimed; ~10 s)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements, each after the timed steps: the per-launch conv2d step (roofline_conv2d), the eager "
+                         "roofline step under --graphs, the scene-geometry GetCost leg, the batch sweep, the GetCost ceiling probe and the CPU "
+                         "baseline (cfg2); the per-sample comparison of --scene-mode; the backward rooflines of cfg4.  Without it a run sets up, "
+                         "warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32), at most 64 MB: a fixed, seeded sample of the "
+                         "batch items when the whole is larger")
+    ap.add_argument("--no-batch-sweep", action="store_true", help="(--full) skip the batch sweep")
+    ap.add_argument("--conv-table", action="store_true", help="print the per-shape table of the step's conv2d launches to stderr "
+                                                              "(runs the per-launch conv2d step also without --full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-probe", action="store_true", help="(--full) skip the GetCost ceiling-probe / random-line-gather legs (untimed; ~10 s)")
     ap.add_argument("--cpu-forwards", type=int, default=8)
     ap.add_argument("--cpu-threads", type=int, default=32, help="threads of the CPU baseline leg (more than ~32 is slower at batch 1)")
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--backend", default="nccl", help=argparse.SUPPRESS)        # "gloo" + --stub-model: the CPU test of the N>1 plumbing
     ap.add_argument("--stub-model", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    # the diffusion noise (torch.randn on the device) and the training step's draws come from torch's generators: seeded, so that the
+    # same arguments give the same inputs and outputs from run to run (--dump-outputs)
+    torch.manual_seed(0)
     if a.cpu_baseline_only:
         return cpu_baseline(a)
     if a.gpus > 1 and "RANK" not in os.environ:
@@ -610,27 +671,31 @@ def main():
 
     with torch.no_grad():
         for _ in range(a.warmup):
-            model(imgs, proj, dv)
+            out = model(imgs, proj, dv)
         eng.ops.timers = {"dmvs_getcost_quad_f32": [], "dmvs_warp_corr_init_quad_f32": []}
-        elapsed = timed_steps(lambda: model(imgs, proj, dv), a.steps, 0, barrier)
+        elapsed, out = timed_steps(lambda: model(imgs, proj, dv), a.steps, 0, barrier)
     timers, eng.ops.timers = eng.ops.timers, None
     elapsed = shard.barrier_and_max(elapsed, dev)      # whole-job time = slowest rank
+    dumped = dump_outputs(out, a.dump_outputs, B) if (a.dump_outputs and rank == 0) else None
+    del out
     model.hip_graphs = False                           # the per-kernel event legs below need the eager launch sequence
-    if a.graphs:      # no per-launch events inside a graph replay: one extra eager step for the roofline legs
+    if a.graphs and a.full:      # no per-launch events inside a graph replay: one extra eager step for the roofline legs
         with torch.no_grad():
             eng.ops.timers = {k: [] for k in timers}
             model(imgs, proj, dv)
             torch.cuda.synchronize()
         timers, eng.ops.timers = eng.ops.timers, None
     # one extra, untimed step with an event pair around every conv2d launch (kept out of the timed region: ~200 launches)
-    with torch.no_grad():
-        eng.ops.timers = {"dmvs_conv2d_f32": []}
-        t1 = time.perf_counter()
-        model(imgs, proj, dv)
-        torch.cuda.synchronize()
-        conv_step_s = time.perf_counter() - t1
-    timers.update(eng.ops.timers)
-    eng.ops.timers = None
+    conv_step_s = None
+    if a.full or a.conv_table:
+        with torch.no_grad():
+            eng.ops.timers = {"dmvs_conv2d_f32": []}
+            t1 = time.perf_counter()
+            model(imgs, proj, dv)
+            torch.cuda.synchronize()
+            conv_step_s = time.perf_counter() - t1
+        timers.update(eng.ops.timers)
+        eng.ops.timers = None
     # per-shape table of the step's conv2d launches: TFLOP/s against the fp32-MFMA peak AND algorithmic GB/s against the HBM peak; a
     # row's binding resource is the larger of the two fractions (a 1x1 layer moves 4 bytes per 2 x cout flops: HBM; a 3x3 layer at 32+
     # channels: the matrix pipe).  `sum` = (t_mfma + t_hbm) / t: near 1.0 the launch pays its matrix time PLUS its memory time (no overlap).
@@ -650,9 +715,9 @@ def main():
         print("B cin cout kh kw s Hout Wout mode gated | launches  ms/step  TFLOP/s  frac_mfma  GB/s  frac_hbm  bound  sum", file=sys.stderr)
         for r in conv_rows:
             print(*r["shape"], "|", r["launches"], r["ms"], r["tflops"], r["frac_mfma"], int(r["gbs"]), r["frac_hbm"], r["bound"], r["sum"], file=sys.stderr)
-    scene = scene_geometry_getcost(eng.ops, B, H, W, S, args.CostNum[1]) if (rank == 0 and a.config == "cfg2") else None
+    scene = scene_geometry_getcost(eng.ops, B, H, W, S, args.CostNum[1]) if (a.full and rank == 0 and a.config == "cfg2") else None
 
-    sweep = batch_sweep(model, make_batch) if (rank == 0 and world == 1 and not a.no_batch_sweep and a.config == "cfg2") else None
+    sweep = batch_sweep(model, make_batch) if (a.full and rank == 0 and world == 1 and not a.no_batch_sweep and a.config == "cfg2") else None
     maps = B * a.steps * world
     value = maps / elapsed
     gc_ms = [s.elapsed_time(e) for s, e in timers["dmvs_getcost_quad_f32"]]
@@ -680,7 +745,7 @@ def main():
         alg_init = sum(timers["_warp_init_bytes"]) / len(timers["_warp_init_bytes"])
     achieved = alg / gc_avg_s / 1e9 if gc_avg_s > 0 else 0.0
     wi_avg_s = sum(wi_ms) / max(1, len(wi_ms)) * 1e-3
-    cv_s = sum(s.elapsed_time(e) for s, e in timers["dmvs_conv2d_f32"]) * 1e-3
+    cv_s = sum(s.elapsed_time(e) for s, e in timers.get("dmvs_conv2d_f32", [])) * 1e-3
     cv_flops = sum(timers.get("_conv2d_flops", []))
 
     # HBM traffic per getcost launch from the PMC passes (rocprofv3 cannot run inside the timed process); only
@@ -699,7 +764,7 @@ def main():
 
     # the memory-system ceiling of GetCost's address stream, measured by this process in untimed legs (see getcost_ceiling_probe)
     ceiling = None
-    if rank == 0 and world == 1 and a.config == "cfg2" and not a.no_probe:
+    if a.full and rank == 0 and world == 1 and a.config == "cfg2" and not a.no_probe:
         try:
             ceiling = getcost_ceiling_probe(model, eng, imgs, proj, dv, {"getcost": alg, "src_texels": B * S * h2 * w2})
             ceiling["product_in_step_avg_us"] = round(gc_avg_s * 1e6, 2)
@@ -741,7 +806,8 @@ def main():
                                "algorithmic_bytes_per_launch": alg_init, "avg_launch_us": round(wi_avg_s * 1e6, 2)},
         "roofline_scene_geometry": scene,
         # where the step's time actually goes: all 2-D convolution launches together, priced against the fp32 arithmetic the reference does
-        "roofline_conv2d": {"kernel": "conv2d_mfma_kernel<*> / conv1x1_px4_kernel<*> (all 2-D convolution launches of the step)", "bound": "mfma",
+        "roofline_conv2d": None if conv_step_s is None else {
+                            "kernel": "conv2d_mfma_kernel<*> / conv1x1_px4_kernel<*> (all 2-D convolution launches of the step)", "bound": "mfma",
                             "achieved": round(cv_flops / cv_s / 1e12, 2) if cv_s > 0 else 0.0, "peak": FP32_MFMA_PEAK_TFS,
                             "unit": "TFLOP/s", "frac": round(cv_flops / cv_s / 1e12 / FP32_MFMA_PEAK_TFS, 4) if cv_s > 0 else 0.0,
                             "launches_timed": len(timers["dmvs_conv2d_f32"]),
@@ -752,7 +818,10 @@ def main():
                             "ms_by_binding_roof": {k: round(sum(r["ms"] for r in conv_rows if r["bound"] == k), 3) for k in ("mfma", "hbm")},
                             "rows": [[*r["shape"][:8], r["launches"], r["ms"], r["frac_mfma"], r["frac_hbm"], r["bound"]] for r in conv_rows[:24]],
                             "rows_columns": "B cin cout kh kw stride Hout Wout launches ms_per_step frac_of_fp32_mfma_peak frac_of_hbm_peak binding_roof (top 24 shapes by time)"},
+        "full": a.full, "dumped_outputs": dumped,
     }
+    if not gc_ms:       # --graphs without --full: no per-launch events inside a graph replay, and no eager step of their own
+        result["roofline"] = result["roofline_warp_init"] = None
 
     if a.config != "cfg2":
         which = "configs[2]" if a.config == "cfg3" else "configs[4]: Tanks&Temples full resolution, scene-sharded inference"
@@ -761,9 +830,10 @@ def main():
                                         f"{prec} feature storage, {arith} matrix arithmetic in the 2-D convolutions (fp32 accumulation), everything else "
                                         f"fp32 (BASELINE.json {which}; not the headline configuration)")
         result["dtype"] = "bf16" if arith == "bf16" else "f32"
-        result["roofline"]["kernel"] = "GetCost: getcost_quad_kernel<32,4> + <16,4> (stage 2 and stage 3 launches, bytes averaged per launch)"
         result["roofline_conv2d"] = None
-        result["roofline_warp_init"]["kernel"] = result["roofline_warp_init"]["kernel"].replace("<48>", "<48> D=%d" % nd_initial)
+        if result["roofline"]:
+            result["roofline"]["kernel"] = "GetCost: getcost_quad_kernel<32,4> + <16,4> (stage 2 and stage 3 launches, bytes averaged per launch)"
+            result["roofline_warp_init"]["kernel"] = result["roofline_warp_init"]["kernel"].replace("<48>", "<48> D=%d" % nd_initial)
         if scene_note:
             result["config"]["scene_sharding"] = scene_note
             result["config"]["multi_gpu"] = ("measured on %d GPU(s) in this run" % world) + ("" if world > 1 else
@@ -780,7 +850,7 @@ def main():
         result["config"]["conv_arith_note"] = ("split = fp32-accurate products from bf16 triples (hi + mid + lo, six partial products down to 2^-18, fp32 "
                                                "accumulation) in the multi-tap 2-D convolutions where faster; measured against fp64 as close as the exact-fp32 "
                                                "kernels (profiles/r6_split_accuracy.txt); --conv-arith fp32 runs exact fp32 MFMAs everywhere")
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and a.config == "cfg2":
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and a.config == "cfg2":
         # the CPU leg runs in a child process with a hard time limit so that an oversubscribed or slow
         # host can never stall the GPU measurement
         import subprocess

@@ -106,3 +106,46 @@ def test_bench_spawns_ranks_for_every_line(tmp_path):
             sh = r["scene_sharding"]
             assert sh["scenes_total"] == 4 and sh["scenes_of_rank0"] == ["scene00", "scene02"]
             assert abs(r["value"] - 4 * 2 * 3 / (r["ms_per_step"] * 3e-3)) < 1e-2 * r["value"]      # all ranks' scenes x batch x steps / whole time
+
+
+def test_bench_dump_outputs_and_steps(tmp_path):
+    """`--steps K` times exactly K steps and `--dump-outputs DIR` writes what the last timed step returned as float32 .npy files; the same
+    arguments give the same arrays from run to run (seeded generators).  Here with the stand-in model; on the GPU box the same code writes the
+    depth maps and confidences of the timed forward."""
+    import json
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
+    arrays = []
+    for run in ("a", "b"):
+        cp = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--stub-model",
+                             "--dump-outputs", str(tmp_path / run)], env=env, capture_output=True, text=True, timeout=120)
+        assert cp.returncode == 0, cp.stderr[-2000:]
+        lines = [ln for ln in cp.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, cp.stdout
+        r = json.loads(lines[0])
+        assert r["steps"] == 4 and r["ms_per_step"] > 0 and r["dumped_outputs"]["arrays"] == ["stub_output"]
+        arrays.append(np.load(tmp_path / run / "stub_output.npy"))
+    assert arrays[0].dtype == np.float32 and arrays[0].shape == (64, 64)
+    assert np.array_equal(arrays[0], arrays[1])
+
+
+def test_bench_dump_outputs_samples_large_outputs(tmp_path):
+    """outputs larger than the budget are cut down to one fixed, seeded sample of batch items, the same rows of every batched array"""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    B = 96
+    g = torch.Generator().manual_seed(1)
+    out = {"depth": [torch.rand(B, 64, 80, generator=g), torch.rand(B, 512, 640, generator=g)], "conf": [],
+           "photometric_confidence": [torch.rand(B, 512, 640, generator=g, dtype=torch.float64)], "scalar": torch.ones(3)}
+    rec = [bench.dump_outputs(out, str(tmp_path / run), B) for run in ("a", "b")]
+    assert rec[0] == dict(rec[1], dir=rec[0]["dir"]) and rec[0]["arrays"] == ["depth_0", "depth_1", "photometric_confidence_0", "scalar"]
+    items = rec[0]["batch_items"]
+    assert items == sorted(items) and 0 < len(items) < B
+    total = sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a"))
+    assert bench.DUMP_BUDGET_BYTES * 0.8 < total < 64 * 10 ** 6
+    pc = np.load(tmp_path / "a" / "photometric_confidence_0.npy")
+    assert pc.dtype == np.float64 and np.array_equal(pc, out["photometric_confidence"][0][items].numpy())
+    assert np.array_equal(np.load(tmp_path / "a" / "depth_0.npy"), out["depth"][0][items].numpy())
+    assert np.array_equal(np.load(tmp_path / "a" / "scalar.npy"), np.ones(3, np.float32))

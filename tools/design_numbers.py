@@ -15,7 +15,7 @@ def block():
     cp, sw, cb, cv = rf["ceiling_probe"], line["batch_sweep_ms_per_map"], line["cpu_baseline"], line["roofline_conv2d"]
     tr = rf["traffic"]
     rg = cp["random_line_gather"]
-    return f"""End-of-round numbers (1 x MI355X, `profiles/r6_bench_line.json` = the default `python bench.py --conv-table` of the round's last GPU session,
+    return f"""End-of-round numbers (1 x MI355X, `profiles/r6_bench_line.json` = the full line (`python bench.py --full --conv-table`) of the round's last GPU session,
 `tools/sessions/r6_final.sh`: the whole GPU suite with `-x` green, `smoke()`, this command, the rocprofv3 kernel stats and PMC passes of the same
 command, the second lines; no `csrc/` / `include/` change after it): **{round(line['value'])} depth-maps/s** at the default 96 reference views per step
 ({line['ms_per_step']:.1f} ms per step, `conv_arith` = {line['config'].get('conv_arith')}; round 5: 1313 / 73.1 on the driver's run, round 4: 1299, round 3: 1200, round 2: 1118, round 1: 848 at B=16;

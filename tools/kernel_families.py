@@ -1,8 +1,8 @@
 """Per-family split of a rocprofv3 kernel_stats.csv of a bench.py run: python tools/kernel_families.py <csv> <forwards>
 
-<forwards> = model forwards in the profiled process (bench.py: warm-up + timed steps + 1 per-conv-event step), so that the
-totals print as ms per forward; without it the totals are those of the whole profiled run and are labelled so.  Families: conv2d (incl. the direct 1x1 kernel), conv3d, stem, getcost (NB: includes bench.py's
-untimed scene-geometry side measurement), warp_init, GroupNorm, other."""
+<forwards> = model forwards in the profiled process (bench.py: warm-up + timed steps; with --full + 1 per-conv-event step), so that the
+totals print as ms per forward; without it the totals are those of the whole profiled run and are labelled so.  Families: conv2d (incl. the direct 1x1 kernel), conv3d, stem, getcost (NB: with --full
+includes bench.py's untimed scene-geometry side measurement), warp_init, GroupNorm, other."""
 import csv
 import sys
 
