@@ -746,3 +746,29 @@ class Ops:
         bump_weights_generation()         # parameters are rewritten in place
         self._call("dmvs_adamw_step_f32", _ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), lr, beta1, beta2, eps, wd, step,
                    grad_scale, _ptr(sumsq), max_norm, self.stream())
+
+    # ------------------------------------------------------------------ COLMAP import: view selection
+    def view_scores(self, xyz, offsets, images, mult, centres, theta0=5.0, sigma1=1.0, sigma2=10.0):
+        """dmvs_view_select_scores_f64: the [N,N] fp64 pair scores of colmap_input.py:374-390 from a point -> image CSR (include/dmvs.h).
+        xyz [P,3] / centres [N,3] fp64, offsets [P+1] int64, images / mult [E] int32, all on this binding's device."""
+        for t, dt in ((xyz, torch.float64), (centres, torch.float64), (offsets, torch.int64), (images, torch.int32), (mult, torch.int32)):
+            if t.dtype != dt or not t.is_contiguous() or t.device != self.device:
+                raise _lib.DmvsError(f"view_scores: expected a contiguous {dt} tensor on {self.device}, got {t.dtype} on {t.device}")
+        N, P = int(centres.shape[0]), int(xyz.shape[0])
+        if not 1 <= N <= _lib.VIEW_SELECT_MAX_IMAGES:
+            raise _lib.DmvsError(f"view_scores: {N} images; the score matrix supports 1..{_lib.VIEW_SELECT_MAX_IMAGES}")
+        if offsets.numel() != P + 1 or images.numel() != mult.numel():
+            raise _lib.DmvsError("view_scores: offsets must have P+1 entries and images / mult one per CSR entry")
+        if images.numel():            # the fixed-point range: every image's total multiplicity stays below 2^23
+            per_image = torch.zeros(N, dtype=torch.int64, device=self.device).index_add_(0, images.long().clamp(0, N - 1), mult.long())
+            if int(per_image.max()) >= _lib.VIEW_SELECT_MAX_LIST:
+                raise _lib.DmvsError(f"view_scores: an image lists {int(per_image.max())} points; at most {_lib.VIEW_SELECT_MAX_LIST - 1} are supported")
+        L = offsets[1:] - offsets[:-1]
+        pair_off = torch.zeros(P + 1, dtype=torch.int64, device=self.device)
+        torch.cumsum(L * (L - 1) // 2, 0, out=pair_off[1:])
+        terms = int(pair_off[-1]) if P else 0
+        ws = torch.empty(max(1, N * (N - 1) // 2), dtype=torch.int64, device=self.device)
+        out = self.empty(N, N, dtype=torch.float64)
+        self._call("dmvs_view_select_scores_f64", _ptr(xyz), _ptr(offsets), _ptr(images), _ptr(mult), _ptr(pair_off), P, terms, _ptr(centres), N,
+                   float(theta0), float(sigma1), float(sigma2), _ptr(ws), _ptr(out), self.stream())
+        return out

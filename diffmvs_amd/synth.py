@@ -15,6 +15,7 @@ Sample contract mirrored: reference datasets/mvs.py:129-210
 """
 from __future__ import annotations
 
+import os
 import zlib
 from types import SimpleNamespace
 
@@ -345,3 +346,68 @@ def scene_batch(scene: dict, ref_ids):
         p[:, :, 1, :3, :3] = Ks
         proj[sname] = p
     return imgs, proj, scene["depth_values"][None].repeat(B, 1), view_ids
+
+
+# --------------------------------------------------------------------------- the same scene as a COLMAP sparse model (tests of diffmvs_amd.colmap)
+def scene_plane(seed: int = 0):
+    """(d0, a, c) of synth_scene(seed)'s plane  z = d0 + a x + c y  (world frame), drawn as synth_scene draws them"""
+    rs = np.random.RandomState(1000003 * seed + 101)
+    d0 = rs.uniform(560.0, 760.0)
+    a, c = rs.uniform(-0.25, 0.25, 2)
+    return d0, a, c
+
+
+def _rotation_to_quaternion(R: np.ndarray) -> tuple:
+    """unit quaternion (w, x, y, z) of a rotation matrix, w >= 0 (COLMAP's convention); Shepperd's branch on the largest of
+    w, x, y, z, so that no component comes out of a cancelling square root"""
+    t = np.trace(R)
+    d = [1.0 + t, 1.0 + R[0, 0] - R[1, 1] - R[2, 2], 1.0 - R[0, 0] + R[1, 1] - R[2, 2], 1.0 - R[0, 0] - R[1, 1] + R[2, 2]]
+    k = int(np.argmax(d))
+    s = 2.0 * np.sqrt(d[k])
+    if k == 0:
+        q = [s / 4, (R[2, 1] - R[1, 2]) / s, (R[0, 2] - R[2, 0]) / s, (R[1, 0] - R[0, 1]) / s]
+    elif k == 1:
+        q = [(R[2, 1] - R[1, 2]) / s, s / 4, (R[0, 1] + R[1, 0]) / s, (R[0, 2] + R[2, 0]) / s]
+    elif k == 2:
+        q = [(R[0, 2] - R[2, 0]) / s, (R[0, 1] + R[1, 0]) / s, s / 4, (R[1, 2] + R[2, 1]) / s]
+    else:
+        q = [(R[1, 0] - R[0, 1]) / s, (R[0, 2] + R[2, 0]) / s, (R[1, 2] + R[2, 1]) / s, s / 4]
+    q = np.array(q) / np.linalg.norm(q)
+    return tuple(float(v) for v in (q if q[0] >= 0 else -q))
+
+
+def export_colmap(scene: dict, root: str, seed: int = 0, n_points: int = 4000, ext: str = ".bin") -> None:
+    """synth_scene(..., seed=seed) as a COLMAP workspace: <root>/images/view_%03d.png (the rendered images) and
+    <root>/sparse/{cameras,images,points3D}<ext>: one PINHOLE camera (the scene's K), every view's E as a quaternion and a
+    translation, and n_points points sampled on the scene's plane; each image lists the points that project inside it with
+    positive depth."""
+    from PIL import Image as PILImage
+    from . import colmap as CM
+    d0, a, c = scene_plane(seed)
+    rs = np.random.RandomState(7 * seed + 3)
+    xy = np.stack([rs.uniform(-420.0, 420.0, n_points), rs.uniform(-360.0, 360.0, n_points)], 1)
+    xyz = np.concatenate([xy, (d0 + a * xy[:, 0] + c * xy[:, 1])[:, None]], 1)
+    imgs = scene["images"].numpy()
+    V, _, H, W = imgs.shape
+    K = scene["K"][0].double().numpy()
+    os.makedirs(os.path.join(root, "images"), exist_ok=True)
+    images, tracks = [], [[] for _ in range(n_points)]
+    for v in range(V):
+        name = "view_%03d.png" % v
+        PILImage.fromarray((np.clip(imgs[v].transpose(1, 2, 0), 0, 1) * 255).astype(np.uint8)).save(os.path.join(root, "images", name))
+        E = scene["E"][v].double().numpy()
+        Xc = xyz @ E[:3, :3].T + E[:3, 3]
+        z = Xc[:, 2]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            u, w = K[0, 0] * Xc[:, 0] / z + K[0, 2], K[1, 1] * Xc[:, 1] / z + K[1, 2]
+        vis = np.nonzero((z > 0) & (u >= 0) & (u < W) & (w >= 0) & (w < H))[0]
+        for j, r in enumerate(vis):
+            tracks[r].append((v + 1, j))
+        images.append(CM.Image(v + 1, _rotation_to_quaternion(E[:3, :3]), tuple(float(x) for x in E[:3, 3]), 1, name,
+                               np.stack([u[vis], w[vis]], 1), (vis + 1).astype(np.int64)))
+    toff = np.zeros(n_points + 1, np.int64)
+    np.cumsum([len(t) for t in tracks], out=toff[1:])
+    track = np.array([t for tr in tracks for t in tr], np.int32).reshape(-1, 2)
+    pts = CM.Points3D(np.arange(1, n_points + 1, dtype=np.int64), xyz, np.full((n_points, 3), 128, np.uint8), np.zeros(n_points), toff, track)
+    cam = CM.Camera(1, "PINHOLE", W, H, (float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2])))
+    CM.write_model(CM.Model({1: cam}, images, pts), os.path.join(root, "sparse"), ext)

@@ -471,6 +471,27 @@ int dmvs_adamw_step_f32(float* param, const float* grad, float* exp_avg, float* 
 /* NCHW -> NHWC for features that did not come out of dmvs_conv2d_f32 channel-last */
 int dmvs_nchw_to_nhwc_f32(const float* in, float* out, int32_t B, int32_t C, int32_t HW, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * View selection of the COLMAP import (added under ABI 4, additive: no existing descriptor or arity changed).  Replaces
+ * colmap_input.py:374-390 calc_score for every image pair at once.  Images are numbered by their position in images.bin.
+ *   xyz [P,3] fp64: the points;  centres [N,3] fp64: camera centres -R^T t
+ *   point -> image CSR built from the images' point3D_ids lists (entries of -1 dropped): offsets [P+1] int64, images [E] int32
+ *        ascending and unique within a point, mult [E] int32 = how often that image lists the point
+ *   pair_offsets [P+1] int64: exclusive prefix sum of L_p (L_p - 1) / 2, L_p = offsets[p+1] - offsets[p];  terms = pair_offsets[P]
+ *   workspace: N (N - 1) / 2 uint64 (the fixed-point upper triangle), zeroed here;  score [N,N] fp64: symmetric, zero diagonal.
+ * Pair (i, j), i < j, scores sum over points seen by both of mult_i * exp(-(th - theta0)^2 / (2 s^2)), s = sigma1 if th <= theta0
+ * else sigma2, th = degrees(acos(dot(c_i - p, c_j - p) / |c_i - p| / |c_j - p|)) in fp64: the reference counts a point once per
+ * entry in the LOWER-indexed image's list.  Two deviations from the reference: the cosine is clamped to [-1, 1] (the reference
+ * gives NaN when it rounds past), and a point at a camera centre contributes 0 (the reference divides by zero).
+ * Terms are summed as max(1, round(f 2^40)) (f > 0) in uint64 with integer atomics: the result is bitwise independent of launch order and shape.
+ * The caller keeps every image's total multiplicity below DMVS_VIEW_SELECT_MAX_LIST (no overflow of the fixed point).
+ * DMVS_EINVAL: N outside [1, DMVS_VIEW_SELECT_MAX_IMAGES], sigma <= 0, NULL operands. */
+#define DMVS_VIEW_SELECT_MAX_IMAGES 16384
+#define DMVS_VIEW_SELECT_MAX_LIST (1 << 23)
+int dmvs_view_select_scores_f64(const double* xyz, const int64_t* offsets, const int32_t* images, const int32_t* mult,
+                                const int64_t* pair_offsets, int64_t P, int64_t terms, const double* centres, int32_t N,
+                                double theta0, double sigma1, double sigma2, uint64_t* workspace, double* score, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
