@@ -1,0 +1,333 @@
+"""Scores of a fused point cloud against a ground-truth cloud: accuracy, completeness, F-score.
+
+    python -m diffmvs_amd.cloud_eval --pred pc.ply --gt gt.ply --max_dist 20 --density 0.2 --thresholds 1 2 5 \\
+        [--dtu_obs_mask ObsMask/ObsMask1_10.mat --dtu_plane ObsMask/Plane1.mat | --roi roi.npz] [--error_ply out.ply]
+
+The definitions are those of the DTU scorer (accuracy = mean distance from the prediction to the ground truth over the points
+closer than max_dist, completeness = the same from the ground truth to the prediction, overall = their mean) and of the
+Tanks&Temples / ETH3D F-score (precision / recall = the share of prediction / ground-truth points closer than a threshold,
+fscore = 2 P R / (P + R)).  Both are two nearest-neighbour searches between the clouds; they run on the GPU
+(dmvs_cloud_nn_dist_f32, dmvs_cloud_stats_f32: csrc/cloud_eval.hip), torch sorts the points into the uniform grid the kernel
+walks.  The official MATLAB / Tanks&Temples tools remain the authority for published numbers: `voxel_downsample` below is NOT the
+DTU scorer's thinning (see its docstring), and the Tanks&Temples alignment and cropping step is not part of this module."""
+from __future__ import annotations
+
+import argparse
+import json
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import formats as IO
+from .ops import Ops
+
+NEAR_RINGS = 4      # nn_distance: the fine pass searches this many cells far ...
+FAR_RINGS = 8       # ... the coarse pass covers max_dist in this many
+
+
+# ------------------------------------------------------------------------------------------ grid
+def _bits(n: int) -> int:
+    return max(0, int(n) - 1).bit_length()
+
+
+def _cells(xyz: torch.Tensor, origin, h: float) -> torch.Tensor:
+    """integer cell coordinates floor((p - origin) / h) in fp64: the arithmetic the kernel repeats for its queries"""
+    o = torch.tensor(list(origin), dtype=torch.float64, device=xyz.device)
+    return torch.floor((xyz.double() - o) / float(h)).long()
+
+
+def _key(cells: torch.Tensor, dims) -> torch.Tensor:
+    bx, by = _bits(dims[0]), _bits(dims[1])
+    return (cells[:, 2] << (bx + by)) | (cells[:, 1] << bx) | cells[:, 0]
+
+
+def build_grid(target: torch.Tensor, cell: float) -> dict:
+    """sort `target` [M,3] fp32 into a uniform grid of cell side `cell` whose origin is the cloud's minimum corner.
+    -> {target (sorted), keys [C], start [C+1], origin, dims, cell}: the operands of Ops.cloud_nn_dist"""
+    if not (cell > 0 and math.isfinite(cell)):
+        raise ValueError(f"cell size must be positive and finite, got {cell}")
+    dev = target.device
+    if target.shape[0] == 0:
+        z = torch.zeros(0, dtype=torch.int64, device=dev)
+        return {"target": target.reshape(0, 3).contiguous(), "keys": z, "start": torch.zeros(1, dtype=torch.int64, device=dev),
+                "origin": (0.0, 0.0, 0.0), "dims": (1, 1, 1), "cell": float(cell)}
+    if not bool(torch.isfinite(target).all()):
+        raise ValueError("the target cloud holds non-finite coordinates")
+    lo = target.min(0).values.double()
+    origin = tuple(float(v) for v in lo.cpu())
+    cells = _cells(target, origin, cell)
+    dims = tuple(int(v) + 1 for v in cells.max(0).values.cpu())
+    if sum(_bits(n) for n in dims) > _lib.CLOUD_MAX_KEY_BITS:
+        raise ValueError(f"a grid of {dims} cells of side {cell} exceeds the {_lib.CLOUD_MAX_KEY_BITS}-bit key: raise the cell size")
+    key, order = torch.sort(_key(cells, dims))
+    keys, counts = torch.unique_consecutive(key, return_counts=True)
+    start = torch.zeros(keys.numel() + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(counts, 0, out=start[1:])
+    return {"target": target[order].contiguous(), "keys": keys, "start": start, "origin": origin, "dims": dims, "cell": float(cell)}
+
+
+def grid_nn(ops: Ops, query: torch.Tensor, grid: dict, max_dist: float, work: bool = False):
+    """one launch of the kernel on a built grid: the queries are sorted by the grid's key first (neighbouring lanes then read the
+    same cells) and the results scattered back.  -> dist [Q] fp32 (and work [Q,2] int32 with work=True)"""
+    Q = query.shape[0]
+    if Q and grid["keys"].numel():
+        dims = grid["dims"]
+        hi = torch.tensor([n - 1 for n in dims], device=query.device)
+        c = _cells(torch.nan_to_num(query, nan=0.0, posinf=3e38, neginf=-3e38), grid["origin"], grid["cell"])
+        order = torch.sort(_key(torch.minimum(c.clamp_min_(0), hi), dims)).indices
+        q = query[order].contiguous()
+    else:
+        order, q = None, query.contiguous()
+    res = ops.cloud_nn_dist(q, grid["target"], grid["keys"], grid["start"], grid["origin"], grid["cell"], grid["dims"], max_dist, work=work)
+    if order is None:
+        return res
+    d, wk = res if work else (res, None)
+    out = torch.empty_like(d)
+    out[order] = d
+    if not work:
+        return out
+    wout = torch.empty_like(wk)
+    wout[order] = wk
+    return out, wout
+
+
+def estimate_spacing(points: torch.Tensor, probe: float) -> float:
+    """typical distance between neighbouring points of a SURFACE sample: with n points in an occupied probe cell of side s, a
+    surface patch of area ~ s^2 holds them at spacing s / sqrt(n)"""
+    if points.shape[0] < 2:
+        return float(probe)
+    lo = points.min(0).values.double()
+    c = torch.floor((points.double() - lo) / probe).long()
+    c = c - c.min(0).values
+    ny, nz = int(c[:, 1].max()) + 1, int(c[:, 2].max()) + 1
+    occupied = torch.unique((c[:, 0] * ny + c[:, 1]) * nz + c[:, 2]).numel()
+    return float(probe / math.sqrt(max(1.0, points.shape[0] / occupied)))
+
+
+def _to_cloud(ops: Ops, x) -> torch.Tensor:
+    t = torch.as_tensor(np.ascontiguousarray(x) if isinstance(x, np.ndarray) else x)
+    if t.dim() != 2 or t.shape[1] != 3:
+        raise ValueError(f"a cloud is an [N,3] array, got {tuple(t.shape)}")
+    return t.to(device=ops.device, dtype=torch.float32).contiguous()
+
+
+def nn_distance(ops: Ops, query, target, max_dist: float, cell: float | None = None, passes: int = 2, stats: dict | None = None) -> torch.Tensor:
+    """min(|q - nearest target|, max_dist) for every query, fp32 [Q] on the binding's device.
+
+    cell: the side of the grid cells; default: twice the target's point spacing (about four surface points per cell), estimated
+    from its density.  It is NOT max_dist: with DTU's protocol max_dist is 100 point spacings, and a cell of that size would be
+    brute force.  But a query with nothing near it has to look through up to (2R + 1)^2 rows of cells, R = ceil(max_dist / cell),
+    to know so.  Hence two passes (passes=2): the first searches the fine grid only NEAR_RINGS cells far (the kernel's clamp makes
+    that a search of its own); the queries it leaves at its clamp -- outliers and holes, a few per cent of a fused cloud -- go
+    through a second launch on a coarse grid of cell max_dist / FAR_RINGS.  passes=1 is one launch on the grid of side `cell`
+    with the full max_dist.  The result does not depend on `cell` or `passes` (the kernel returns the exact minimum of the fp32
+    distances).  stats: a dict that receives the early-exit figures (tools/cloud_eval_bench.py)."""
+    if not (max_dist > 0 and math.isfinite(max_dist)):
+        raise ValueError(f"max_dist must be positive and finite, got {max_dist}")
+    query, target = _to_cloud(ops, query), _to_cloud(ops, target)
+    if cell is None:
+        cell = min(float(max_dist), 2.0 * estimate_spacing(target, max_dist / FAR_RINGS)) if target.shape[0] else float(max_dist)
+    cell = float(cell)
+    near = float(np.float32(NEAR_RINGS * cell))      # (the kernel's clamp is fp32: the unresolved queries sit exactly here)
+    want = stats is not None
+    if passes == 1 or near >= max_dist or target.shape[0] == 0:
+        if math.ceil(max_dist / cell) > _lib.CLOUD_MAX_RINGS:
+            raise ValueError(f"max_dist / cell = {max_dist / cell:.0f} rings; at most {_lib.CLOUD_MAX_RINGS} are supported: raise the cell size")
+        res = grid_nn(ops, query, build_grid(target, cell), max_dist, work=want)
+        if want:
+            stats.update(_work_stats(res[1], None, cell, None))
+            return res[0]
+        return res
+    res = grid_nn(ops, query, build_grid(target, cell), near, work=want)
+    d, wk = res if want else (res, None)
+    far = torch.nonzero(d >= near).squeeze(1)
+    wk2 = None
+    if far.numel():
+        cell2 = max(cell, float(max_dist) / FAR_RINGS)
+        res2 = grid_nn(ops, query[far].contiguous(), build_grid(target, cell2), max_dist, work=want)
+        d[far] = res2[0] if want else res2
+        wk2 = res2[1] if want else None
+    if want:
+        stats.update(_work_stats(wk, wk2, cell, max(cell, float(max_dist) / FAR_RINGS)))
+    return d
+
+
+def _work_stats(wk, wk2, cell, cell2) -> dict:
+    n = max(1, wk.shape[0])
+    out = {"cell": cell, "queries": int(wk.shape[0]), "early_exit_rate": float((wk[:, 0] <= 2).sum()) / n,
+           "mean_targets_tested": float(wk[:, 1].double().mean()) if wk.shape[0] else 0.0}
+    if wk2 is not None:
+        out.update({"far_cell": cell2, "far_queries": int(wk2.shape[0]), "far_share": wk2.shape[0] / n,
+                    "far_mean_targets_tested": float(wk2[:, 1].double().mean())})
+    return out
+
+
+# ------------------------------------------------------------------------------------------ thinning
+def voxel_downsample(xyz, voxel: float):
+    """keep, per occupied voxel of side `voxel` (lattice anchored at the coordinate origin), the point with the lowest input
+    index.  -> (points [K,3], index [K] int64 ascending) on the input's device.
+
+    This STANDS IN for the DTU scorer's thinning and is not the same algorithm: the MATLAB program walks the points in input
+    order and drops every point closer than `voxel` to one it has kept (greedy, serial, order-dependent; kept points are at
+    least `voxel` apart), whereas a voxel lattice keeps points that may be arbitrarily close across a voxel face and about as
+    many per area.  Scores computed after this thinning are therefore close to the official ones, not identical to them."""
+    t = torch.as_tensor(np.ascontiguousarray(xyz) if isinstance(xyz, np.ndarray) else xyz)
+    if not (voxel > 0 and math.isfinite(voxel)):
+        raise ValueError(f"voxel size must be positive and finite, got {voxel}")
+    if t.shape[0] == 0:
+        return t, torch.zeros(0, dtype=torch.int64, device=t.device)
+    c = torch.floor(t.double() / float(voxel)).long()
+    c = c - c.min(0).values
+    n = [int(v) + 1 for v in c.max(0).values.cpu()]
+    if sum(_bits(v) for v in n) > 62:
+        raise ValueError(f"a lattice of {n} voxels of side {voxel} exceeds the 62-bit key")
+    key = (c[:, 2] << (_bits(n[0]) + _bits(n[1]))) | (c[:, 1] << _bits(n[0])) | c[:, 0]
+    skey, order = torch.sort(key, stable=True)      # stable: the first entry of a run of equal keys is the lowest input index
+    first = torch.ones_like(skey, dtype=torch.bool)
+    first[1:] = skey[1:] != skey[:-1]
+    idx = torch.sort(order[first]).values
+    return t[idx], idx
+
+
+# ------------------------------------------------------------------------------------------ region of interest
+def make_roi(mask, origin, resolution: float, plane=None) -> dict:
+    """mask: boolean voxel volume [X,Y,Z]; a point p belongs to voxel round((p - origin) / resolution) (nearest voxel, half away from
+    zero: the DTU scorer's indexing of ObsMask).  plane: optional (a, b, c, d); the half-space kept is a x + b y + c z + d > 0."""
+    mask = np.asarray(mask).astype(bool)
+    if mask.ndim != 3:
+        raise ValueError("the ROI mask is a 3-D boolean volume")
+    return {"mask": mask, "origin": np.asarray(origin, np.float64).reshape(3), "resolution": float(resolution),
+            "plane": None if plane is None else np.asarray(plane, np.float64).reshape(4)}
+
+
+def load_roi(path: str) -> dict:
+    """an ROI saved with numpy.savez(path, mask=, origin=, resolution=[, plane=])"""
+    z = np.load(path, allow_pickle=False)
+    return make_roi(z["mask"], z["origin"], float(z["resolution"]), z["plane"] if "plane" in z.files else None)
+
+
+def load_dtu_roi(obs_mask_mat: str, plane_mat: str | None = None) -> dict:
+    """DTU's ObsMask/ObsMask<scan>_10.mat (ObsMask, BB, Res) and ObsMask/Plane<scan>.mat (P).  Needs scipy for the .mat container."""
+    try:
+        from scipy.io import loadmat
+    except ImportError as e:
+        raise ImportError("load_dtu_roi reads MATLAB .mat files through scipy (scipy.io.loadmat), which is not installed; "
+                          "convert the masks with numpy.savez(mask=, origin=, resolution=, plane=) and use load_roi / --roi instead") from e
+    m = loadmat(obs_mask_mat)
+    plane = None if plane_mat is None else np.asarray(loadmat(plane_mat)["P"], np.float64).reshape(4)
+    return make_roi(m["ObsMask"], np.asarray(m["BB"], np.float64)[0], float(np.asarray(m["Res"]).reshape(-1)[0]), plane)
+
+
+def roi_volume_mask(points: torch.Tensor, roi: dict) -> torch.Tensor:
+    """points [N,3] -> uint8 [N]: 1 where the point's voxel exists and is set"""
+    dev = points.device
+    vol = torch.from_numpy(roi["mask"]).to(dev)
+    u = (points.double() - torch.from_numpy(roi["origin"]).to(dev)) / roi["resolution"]
+    v = (torch.sign(u) * torch.floor(u.abs() + 0.5)).long()
+    shape = torch.tensor(vol.shape, device=dev)
+    inside = ((v >= 0) & (v < shape)).all(1)
+    v = torch.minimum(v.clamp_min(0), shape - 1)
+    return (inside & vol[v[:, 0], v[:, 1], v[:, 2]]).to(torch.uint8).contiguous()
+
+
+def roi_plane_mask(points: torch.Tensor, roi: dict):
+    if roi["plane"] is None:
+        return None
+    p = torch.from_numpy(roi["plane"]).to(points.device)
+    return ((points.double() @ p[:3] + p[3]) > 0).to(torch.uint8).contiguous()
+
+
+# ------------------------------------------------------------------------------------------ metrics
+def fixed_scale(max_dist: float, n: int) -> float:
+    """the largest power of two with max_dist * scale * max(n, 1) < 2^62: the u64 sum of rint(d * scale) cannot overflow"""
+    e = math.floor(math.log2(2.0 ** 62 / (float(max_dist) * max(1, n))))
+    while float(max_dist) * 2.0 ** e * max(1, n) >= 2.0 ** 62:
+        e -= 1
+    return 2.0 ** e
+
+
+def side_stats(ops: Ops, dist: torch.Tensor, valid, max_dist: float, thresholds, blocks: int = 0) -> dict:
+    """one direction's counters -> {points, valid, in_range, out_of_range, sum_fixed, scale, mean, below: [..]} (python ints; mean is None when no point is in range)"""
+    scale = fixed_scale(max_dist, dist.numel())
+    raw = [int(v) for v in ops.cloud_stats(dist, valid, max_dist, thresholds, scale, blocks=blocks).cpu()]
+    n_valid, n_in, s = raw[0], raw[1], raw[2]
+    return {"points": int(dist.numel()), "valid": n_valid, "in_range": n_in, "out_of_range": n_valid - n_in, "sum_fixed": s, "scale": scale,
+            "mean": (s / scale / n_in) if n_in else None, "below": raw[3:]}
+
+
+def evaluate(ops: Ops, pred, gt, max_dist: float, thresholds, density: float | None = None, roi: dict | None = None, cell: float | None = None,
+             return_distances: bool = False) -> dict:
+    """pred, gt: [N,3] clouds (numpy or torch).  density: thin the prediction with voxel_downsample(pred, density) first (the
+    ground truth is taken as it is).  roi (make_roi / load_roi / load_dtu_roi): prediction points outside the volume are left out
+    of accuracy and precision, ground-truth points outside the half-space out of completeness and recall -- both searches still
+    run against the WHOLE other cloud, as the DTU scorer's do.
+    -> accuracy, completeness, overall, thresholds, precision / recall / fscore per threshold, and the counters of both
+    directions under "pred" and "gt" (points, valid, in_range, out_of_range, sum_fixed, scale, below)."""
+    thresholds = [float(t) for t in thresholds]
+    pred, gt = _to_cloud(ops, pred), _to_cloud(ops, gt)
+    n_pred_in = int(pred.shape[0])
+    kept = None
+    if density is not None:
+        pred, kept = voxel_downsample(pred, density)
+        pred = pred.contiguous()
+    if cell is None and density is not None:
+        cell = 2.0 * float(density)
+    valid_p = roi_volume_mask(pred, roi) if roi is not None else None
+    valid_g = roi_plane_mask(gt, roi) if roi is not None else None
+    d_pred = nn_distance(ops, pred, gt, max_dist, cell=cell)
+    d_gt = nn_distance(ops, gt, pred, max_dist, cell=cell)
+    sp, sg = side_stats(ops, d_pred, valid_p, max_dist, thresholds), side_stats(ops, d_gt, valid_g, max_dist, thresholds)
+    precision = [b / sp["valid"] if sp["valid"] else 0.0 for b in sp["below"]]
+    recall = [b / sg["valid"] if sg["valid"] else 0.0 for b in sg["below"]]
+    res = {"accuracy": sp["mean"], "completeness": sg["mean"], "overall": None if None in (sp["mean"], sg["mean"]) else 0.5 * (sp["mean"] + sg["mean"]), "max_dist": float(max_dist),
+           "thresholds": thresholds, "precision": precision, "recall": recall,
+           "fscore": [2 * p * r / (p + r) if p + r > 0 else 0.0 for p, r in zip(precision, recall)],
+           "density": density, "pred_points_read": n_pred_in, "pred": sp, "gt": sg}
+    if return_distances:
+        res["_distances"] = (pred, d_pred, gt, d_gt, kept)
+    return res
+
+
+def error_colours(dist: torch.Tensor, max_dist: float) -> np.ndarray:
+    """clamped distance -> uint8 RGB [N,3]: blue (0) over green to red (max_dist)"""
+    t = (dist.double() / float(max_dist)).clamp(0, 1).cpu().numpy()
+    rgb = np.stack([np.clip(2 * t - 1, 0, 1), np.clip(1 - np.abs(2 * t - 1), 0, 1), np.clip(1 - 2 * t, 0, 1)], -1)
+    return (rgb * 255 + 0.5).astype(np.uint8)
+
+
+def evaluate_files(ops: Ops, pred_ply: str, gt_ply: str, max_dist: float, thresholds, density=None, roi=None, error_ply=None) -> dict:
+    pred, gt = IO.read_ply(pred_ply)[0], IO.read_ply(gt_ply)[0]
+    res = evaluate(ops, pred, gt, max_dist, thresholds, density=density, roi=roi, return_distances=error_ply is not None)
+    if error_ply is not None:
+        p, d = res.pop("_distances")[:2]
+        IO.write_ply(error_ply, p.cpu().numpy(), error_colours(d, max_dist))
+    return res
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--pred", required=True, help="the cloud to score (PLY)")
+    ap.add_argument("--gt", required=True, help="the ground-truth cloud (PLY)")
+    ap.add_argument("--max_dist", type=float, required=True, help="distances are clamped here; points at the clamp count as outliers (DTU: 20)")
+    ap.add_argument("--density", type=float, default=None, help="thin the prediction to one point per voxel of this side first (DTU: 0.2)")
+    ap.add_argument("--thresholds", type=float, nargs="*", default=[], help="F-score thresholds (at most %d)" % _lib.CLOUD_MAX_THRESHOLDS)
+    ap.add_argument("--dtu_obs_mask", default=None, help="DTU ObsMask<scan>_10.mat (needs scipy)")
+    ap.add_argument("--dtu_plane", default=None, help="DTU Plane<scan>.mat (needs scipy)")
+    ap.add_argument("--roi", default=None, help="an ROI saved with numpy.savez(mask=, origin=, resolution=[, plane=])")
+    ap.add_argument("--error_ply", default=None, help="write the (thinned) prediction coloured by its clamped distance")
+    ap.add_argument("--device", default="cuda:0")
+    a = ap.parse_args(argv)
+    if a.roi and (a.dtu_obs_mask or a.dtu_plane):
+        raise SystemExit("--roi and --dtu_obs_mask / --dtu_plane are alternatives")
+    if a.dtu_plane and not a.dtu_obs_mask:
+        raise SystemExit("--dtu_plane needs --dtu_obs_mask")
+    roi = load_roi(a.roi) if a.roi else (load_dtu_roi(a.dtu_obs_mask, a.dtu_plane) if a.dtu_obs_mask else None)
+    res = evaluate_files(Ops.for_device(a.device), a.pred, a.gt, a.max_dist, a.thresholds, density=a.density, roi=roi, error_ply=a.error_ply)
+    print(json.dumps(res), flush=True)
+    return res
+
+
+if __name__ == "__main__":
+    main()

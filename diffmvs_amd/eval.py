@@ -8,6 +8,7 @@ contract), run CasDiffMVS.forward timed between device synchronisations exactly 
 depth_est/*.pfm, conf{i}/*.pfm, cams/*_cam.txt, images/*.jpg in the reference's output layout, so that the reference's
 filter.py -- or this package's GPU consistency filter (--filter, diffmvs_amd.fusion) -- can fuse them.  Scenes shard over
 ranks (one process per GPU, RANK / WORLD_SIZE from the launcher) with no communication.
+With --filter --gt_ply the fused cloud is scored against a ground-truth cloud (accuracy / completeness / F-score: diffmvs_amd.cloud_eval).
 If <testpath>/<scan>/depth_gt/%08d.pfm (+ optional mask/%08d.png) exist, the absolute and relative depth errors of
 utils.py:178-187 / BASELINE.json ("DTU abs-rel") are reported per scene."""
 from __future__ import annotations
@@ -124,6 +125,11 @@ def main(argv=None):
     ap.add_argument("--geo_pixel_thres", type=float, default=1.0, help="reprojection error threshold in pixels")
     ap.add_argument("--geo_depth_thres", type=float, default=0.01, help="relative depth error threshold")
     ap.add_argument("--photo_thres", type=float, nargs="+", default=[0.3, 0.0, 0.0], help="confidence threshold per stage")
+    ap.add_argument("--gt_ply", default=None, help="with --filter: score every fused cloud against this ground-truth PLY ('{scene}' is substituted) "
+                    "with diffmvs_amd.cloud_eval; adds cloud_metrics[scene] to the result")
+    ap.add_argument("--cloud_max_dist", type=float, default=20.0, help="--gt_ply: distances are clamped here (DTU: 20)")
+    ap.add_argument("--cloud_density", type=float, default=None, help="--gt_ply: thin the fused cloud to one point per voxel of this side (DTU: 0.2)")
+    ap.add_argument("--cloud_thresholds", type=float, nargs="*", default=[1.0, 2.0, 5.0], help="--gt_ply: F-score thresholds")
     ap.add_argument("--scene_cache", type=int, default=1, choices=[0, 1],
                     help="1 (default): every image of a scene through FeatureNet once, features resident in HBM; 0: the reference's per-sample order")
     ap.add_argument("--graphs", type=int, default=None, choices=[0, 1],
@@ -174,6 +180,12 @@ def main(argv=None):
             n = fusion.filter_depth(os.path.join(a.testpath, scene), os.path.join(a.outdir, scene), method=a.method, device=device, **kw)
             res.setdefault("fused_points", {})[scene] = n
             res.setdefault("ply", {})[scene] = kw["plyfilename"]
+            if a.gt_ply:
+                from . import cloud_eval
+                from .ops import Ops
+                res.setdefault("cloud_metrics", {})[scene] = cloud_eval.evaluate_files(
+                    Ops.for_device(device), kw["plyfilename"], a.gt_ply.replace("{scene}", scene), a.cloud_max_dist, a.cloud_thresholds,
+                    density=a.cloud_density)
     print(json.dumps(res), flush=True)
     return res
 

@@ -312,3 +312,94 @@ def write_ply(filename: str, xyz: np.ndarray, rgb: np.ndarray) -> None:
         f.write(("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
                  "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n" % n).encode("ascii"))
         f.write(v.tobytes())
+
+
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2",
+              "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
+
+
+def read_ply(filename: str):
+    """-> (xyz float32 [N,3], rgb uint8 [N,3] or None).  Reads `binary_little_endian` and `ascii` PLY files with any scalar
+    vertex properties in any order (normals, confidence, ...); other elements (faces) are skipped, list properties are allowed
+    in them only.  The inverse of write_ply."""
+    with open(filename, "rb") as f:
+        data = f.read()
+    end = data.find(b"end_header")
+    nl = data.find(b"\n", end)
+    if not data.startswith(b"ply") or end < 0 or nl < 0:
+        raise ValueError(f"{filename}: not a PLY file (no 'ply' ... 'end_header' header)")
+    fmt, elements = None, []          # elements: [name, count, [(property, numpy type or None for a list)]]
+    for line in data[:end].decode("ascii", "replace").splitlines()[1:]:
+        w = line.split()
+        if not w or w[0] in ("comment", "obj_info"):
+            continue
+        if w[0] == "format":
+            fmt = w[1]
+        elif w[0] == "element":
+            elements.append([w[1], int(w[2]), []])
+        elif w[0] == "property" and elements:
+            if w[1] == "list":
+                elements[-1][2].append((w[4], None, (_PLY_TYPES.get(w[2]), _PLY_TYPES.get(w[3]))))
+            elif w[1] in _PLY_TYPES:
+                elements[-1][2].append((w[2], _PLY_TYPES[w[1]], None))
+            else:
+                raise ValueError(f"{filename}: unknown PLY property type {w[1]!r}")
+    if fmt not in ("binary_little_endian", "ascii"):
+        raise ValueError(f"{filename}: PLY format {fmt!r} is not supported (binary_little_endian and ascii are)")
+    body, vertex = data[nl + 1:], None
+    pos = 0
+    tokens = body.split() if fmt == "ascii" else None
+    for name, count, props in elements:
+        has_list = any(t is None for _, t, _ in props)
+        if name == "vertex":
+            if has_list:
+                raise ValueError(f"{filename}: list properties in the vertex element are not supported")
+            names = [p for p, _, _ in props]
+            if fmt == "ascii":
+                if pos + count * len(props) > len(tokens):
+                    raise ValueError(f"{filename}: truncated: the header announces {count} vertices")
+                try:
+                    tab = np.array(tokens[pos:pos + count * len(props)], dtype=np.float64).reshape(count, len(props))
+                except ValueError as e:
+                    raise ValueError(f"{filename}: malformed ascii vertex data") from e
+                pos += count * len(props)
+                vertex = {p: tab[:, i] for i, p in enumerate(names)}
+            else:
+                dt = np.dtype([(p, "<" + t) for p, t, _ in props])
+                if pos + count * dt.itemsize > len(body):
+                    raise ValueError(f"{filename}: truncated: the header announces {count} vertices of {dt.itemsize} bytes, "
+                                     f"{len(body) - pos} bytes follow")
+                rec = np.frombuffer(body, dtype=dt, count=count, offset=pos)
+                pos += count * dt.itemsize
+                vertex = {p: rec[p] for p in names}
+            break                      # nothing after the vertices is needed
+        # an element in front of the vertices: step over it
+        if fmt == "ascii":
+            for _ in range(count):
+                for _, t, lst in props:
+                    if pos >= len(tokens):
+                        raise ValueError(f"{filename}: truncated inside element {name!r}")
+                    pos += 1 + (int(tokens[pos]) if t is None else 0)
+        elif not has_list:
+            pos += count * sum(np.dtype(t).itemsize for _, t, _ in props)
+        else:
+            for _ in range(count):
+                for _, t, lst in props:
+                    if t is not None:
+                        pos += np.dtype(t).itemsize
+                        continue
+                    if lst[0] is None or lst[1] is None or pos + np.dtype(lst[0]).itemsize > len(body):
+                        raise ValueError(f"{filename}: truncated or malformed list property in element {name!r}")
+                    n = int(np.frombuffer(body, dtype="<" + lst[0], count=1, offset=pos)[0])
+                    pos += np.dtype(lst[0]).itemsize + n * np.dtype(lst[1]).itemsize
+    if vertex is None:
+        raise ValueError(f"{filename}: no vertex element")
+    if not all(k in vertex for k in ("x", "y", "z")):
+        raise ValueError(f"{filename}: the vertex element has no x / y / z")
+    xyz = np.stack([np.asarray(vertex[k], dtype=np.float32) for k in ("x", "y", "z")], -1)
+    rgb = None
+    for keys in (("red", "green", "blue"), ("r", "g", "b"), ("diffuse_red", "diffuse_green", "diffuse_blue")):
+        if all(k in vertex for k in keys):
+            rgb = np.stack([np.asarray(vertex[k]).astype(np.uint8) for k in keys], -1)
+            break
+    return np.ascontiguousarray(xyz), rgb

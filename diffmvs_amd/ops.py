@@ -772,3 +772,42 @@ class Ops:
         self._call("dmvs_view_select_scores_f64", _ptr(xyz), _ptr(offsets), _ptr(images), _ptr(mult), _ptr(pair_off), P, terms, _ptr(centres), N,
                    float(theta0), float(sigma1), float(sigma2), _ptr(ws), _ptr(out), self.stream())
         return out
+
+    # ------------------------------------------------------------------ point-cloud scoring (diffmvs_amd/cloud_eval.py)
+    def _chk_typed(self, what, *pairs):
+        for t, dt in pairs:
+            if t is not None and (t.dtype != dt or not t.is_contiguous() or t.device != self.device):
+                raise _lib.DmvsError(f"{what}: expected a contiguous {dt} tensor on {self.device}, got {t.dtype} on {t.device}")
+
+    def cloud_nn_dist(self, query, target, cell_keys, cell_start, origin, h, dims, max_dist, work=False):
+        """dmvs_cloud_nn_dist_f32: min(|q - nearest target|, max_dist) per query (include/dmvs.h).  query [Q,3] / target [M,3] fp32 with the
+        targets sorted by cell key, cell_keys [C] / cell_start [C+1] int64, origin 3 floats, dims 3 ints.
+        -> dist [Q] fp32, or (dist, work [Q,2] int32: rings walked, targets tested) with work=True."""
+        self._chk_typed("cloud_nn_dist", (query, torch.float32), (target, torch.float32), (cell_keys, torch.int64), (cell_start, torch.int64))
+        Q, M, Cn = int(query.shape[0]), int(target.shape[0]), int(cell_keys.numel())
+        if query.dim() != 2 or query.shape[1] != 3 or target.dim() != 2 or target.shape[1] != 3:
+            raise _lib.DmvsError("cloud_nn_dist: query and target must be [N,3]")
+        if cell_start.numel() != Cn + 1 or Cn > M or (M > 0 and Cn < 1):
+            raise _lib.DmvsError("cloud_nn_dist: cell_start must have one entry more than cell_keys, and every target a cell")
+        dist = self.empty(Q)
+        wk = torch.empty(Q, 2, dtype=torch.int32, device=self.device) if work else None
+        o = (C.c_double * 3)(*[float(v) for v in origin])
+        d = (C.c_int32 * 3)(*[int(v) for v in dims])
+        self._call("dmvs_cloud_nn_dist_f32", _ptr(query), Q, _ptr(target), M, _ptr(cell_keys), _ptr(cell_start), Cn, o, float(h), d,
+                   float(max_dist), _ptr(dist), _ptr(wk), self.stream())
+        return (dist, wk) if work else dist
+
+    def cloud_stats(self, dist, valid, max_dist, thresholds, scale, blocks=0):
+        """dmvs_cloud_stats_f32 -> [3 + T] int64 on the device: valid points, those with d < max_dist, their fixed-point sum
+        (rint(d * scale) per term), and per threshold the valid points with d < threshold (include/dmvs.h)."""
+        self._chk_typed("cloud_stats", (dist, torch.float32), (valid, torch.uint8))
+        T = len(thresholds)
+        if T > _lib.CLOUD_MAX_THRESHOLDS:
+            raise _lib.DmvsError(f"cloud_stats: {T} thresholds; at most {_lib.CLOUD_MAX_THRESHOLDS} are supported")
+        if valid is not None and valid.numel() != dist.numel():
+            raise _lib.DmvsError("cloud_stats: the validity mask must have one entry per distance")
+        out = torch.empty(3 + T, dtype=torch.int64, device=self.device)
+        thr = (C.c_float * max(1, T))(*[float(t) for t in thresholds])
+        self._call("dmvs_cloud_stats_f32", _ptr(dist), _ptr(valid), dist.numel(), float(max_dist), thr, T, float(scale), int(blocks),
+                   _ptr(out), self.stream())
+        return out

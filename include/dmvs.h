@@ -492,6 +492,40 @@ int dmvs_view_select_scores_f64(const double* xyz, const int64_t* offsets, const
                                 const int64_t* pair_offsets, int64_t P, int64_t terms, const double* centres, int32_t N,
                                 double theta0, double sigma1, double sigma2, uint64_t* workspace, double* score, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Point-cloud scoring (added under ABI 4, additive): the nearest-neighbour searches of the DTU / Tanks&Temples / ETH3D scorers and the
+ * reduction of their distances (diffmvs_amd/cloud_eval.py builds the grid and the metrics).
+ *
+ * dmvs_cloud_nn_dist_f32: dist[i] = min(|query_i - nearest target|, max_dist), fp32 (differences, squares, root; no contraction).
+ *   query [Q,3] fp32;  target [M,3] fp32 SORTED by cell key;  dist [Q] fp32;  work: NULL or [Q,2] int32 (rings walked, targets tested)
+ *   the grid: origin (HOST, 3 doubles), cell side h, dims (HOST, 3 int32: cells along x, y, z, each >= 1).  A point's cell is
+ *        floor(((double)p - origin) / h) per axis in fp64, clamped to the grid for queries;  key = (z << (bx + by)) | (y << bx) | x with
+ *        bx / by = the number of bits that hold dims[0] - 1 / dims[1] - 1
+ *   cell_keys [C] int64: the occupied cells, ascending and unique;  cell_start [C+1] int64: first target of each cell, cell_start[C] = M
+ *   (all three device arrays; every target's cell lies inside dims).
+ * One lane per query walks rings of slabs z = cz -+ r, the occupied rows of a slab and the occupied cells of a row outward, each found by
+ * a binary search in cell_keys, and stops a direction when the gap to it cannot beat the best distance so far (csrc/cloud_eval.hip).  The
+ * result is the minimum over all targets of the fp32 squared distance, whatever h is; M = 0 gives max_dist everywhere.
+ * Worst case (2R + 1)^2 rows per query, R = ceil(max_dist / h): the caller keeps R small by raising h.
+ * DMVS_EINVAL (before any launch): NULL operands, Q / M / C < 0, C > M, h or max_dist not finite or <= 0, a non-finite origin, dims < 1,
+ * R > DMVS_CLOUD_MAX_RINGS, a grid whose key needs more than DMVS_CLOUD_MAX_KEY_BITS bits.
+ *
+ * dmvs_cloud_stats_f32: out [3 + T] uint64 (device, zeroed here) = { valid points, those with d < max_dist, their sum as fixed point
+ *   (each term rint((double)d * scale)), then per threshold the valid points with d < thresholds[t] }.
+ *   dist [N] fp32;  valid: NULL (all) or [N] uint8;  thresholds: HOST array of T <= DMVS_CLOUD_MAX_THRESHOLDS floats
+ *   scale: a positive power of two with max_dist * scale * max(N, 1) < 2^62 (the sum cannot overflow; a term is rounded by at most 0.5 / scale)
+ *   blocks: workgroups of the grid-stride launch, 0 = the library's choice (the result does not depend on it).
+ * Wave shuffles, then one integer atomic per counter per workgroup: bitwise independent of launch order and shape.
+ * DMVS_EINVAL: NULL operands, N < 0, T outside [0, 16], a NaN threshold, max_dist not finite or <= 0, scale not a power of two or beyond the bound. */
+#define DMVS_CLOUD_MAX_RINGS 1024
+#define DMVS_CLOUD_MAX_KEY_BITS 62
+#define DMVS_CLOUD_MAX_THRESHOLDS 16
+int dmvs_cloud_nn_dist_f32(const float* query, int64_t Q, const float* target, int64_t M, const int64_t* cell_keys,
+                           const int64_t* cell_start, int64_t C, const double* origin, double h, const int32_t* dims,
+                           float max_dist, float* dist, int32_t* work, void* stream);
+int dmvs_cloud_stats_f32(const float* dist, const uint8_t* valid, int64_t N, float max_dist, const float* thresholds, int32_t T,
+                         double scale, int32_t blocks, uint64_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
