@@ -8,8 +8,10 @@ closer than max_dist, completeness = the same from the ground truth to the predi
 Tanks&Temples / ETH3D F-score (precision / recall = the share of prediction / ground-truth points closer than a threshold,
 fscore = 2 P R / (P + R)).  Both are two nearest-neighbour searches between the clouds; they run on the GPU
 (dmvs_cloud_nn_dist_f32, dmvs_cloud_stats_f32: csrc/cloud_eval.hip), torch sorts the points into the uniform grid the kernel
-walks.  The official MATLAB / Tanks&Temples tools remain the authority for published numbers: `voxel_downsample` below is NOT the
-DTU scorer's thinning (see its docstring), and the Tanks&Temples alignment and cropping step is not part of this module."""
+walks.  Clouds that do not share a frame and a region of interest yet are aligned and cropped first: --transform T.txt (a 4x4
+alignment), --register MAX_CORR (ICP refinement of it on the GPU) and --crop crop.json (a Tanks&Temples crop volume) -- see
+diffmvs_amd.cloud_register.  The official MATLAB / Tanks&Temples tools remain the authority for published numbers:
+`voxel_downsample` below is NOT the DTU scorer's thinning (see its docstring)."""
 from __future__ import annotations
 
 import argparse
@@ -258,13 +260,20 @@ def side_stats(ops: Ops, dist: torch.Tensor, valid, max_dist: float, thresholds,
 
 
 def evaluate(ops: Ops, pred, gt, max_dist: float, thresholds, density: float | None = None, roi: dict | None = None, cell: float | None = None,
-             return_distances: bool = False) -> dict:
+             return_distances: bool = False, transform=None, crop: dict | None = None, register: dict | None = None) -> dict:
     """pred, gt: [N,3] clouds (numpy or torch).  density: thin the prediction with voxel_downsample(pred, density) first (the
     ground truth is taken as it is).  roi (make_roi / load_roi / load_dtu_roi): prediction points outside the volume are left out
     of accuracy and precision, ground-truth points outside the half-space out of completeness and recall -- both searches still
     run against the WHOLE other cloud, as the DTU scorer's do.
     -> accuracy, completeness, overall, thresholds, precision / recall / fscore per threshold, and the counters of both
-    directions under "pred" and "gt" (points, valid, in_range, out_of_range, sum_fixed, scale, below)."""
+    directions under "pred" and "gt" (points, valid, in_range, out_of_range, sum_fixed, scale, below).
+
+    transform: a 4x4 that moves the prediction into the ground truth's frame first.  register: keyword arguments of
+    cloud_register.register (e.g. {"schedule": [(voxel, max_corr, max_iter)], "with_scale": False}) -- the transform (identity if
+    none) is refined by ICP of the thinned prediction onto the ground truth before it is applied.  crop (cloud_register.make_crop /
+    load_crop_json): moved prediction points outside the volume are left out of accuracy / precision, ground-truth points outside it
+    out of completeness / recall, through the same masks as `roi`.  With any of the three the result also holds "transformation"
+    (and "registration"); without them nothing changes."""
     thresholds = [float(t) for t in thresholds]
     pred, gt = _to_cloud(ops, pred), _to_cloud(ops, gt)
     n_pred_in = int(pred.shape[0])
@@ -274,8 +283,21 @@ def evaluate(ops: Ops, pred, gt, max_dist: float, thresholds, density: float | N
         pred = pred.contiguous()
     if cell is None and density is not None:
         cell = 2.0 * float(density)
+    reg = None
+    if transform is not None or crop is not None or register is not None:
+        from . import cloud_register as CR
+        if register is not None:
+            reg = CR.register(ops, pred, gt, init=transform, crop=crop, **register)
+            transform = np.array(reg["transformation"])
+        if transform is not None:
+            transform = np.array(transform, np.float64).reshape(4, 4)
+            pred = CR.apply_transform(pred, transform)
     valid_p = roi_volume_mask(pred, roi) if roi is not None else None
     valid_g = roi_plane_mask(gt, roi) if roi is not None else None
+    if crop is not None:
+        cp, cg = CR.crop_mask(ops, pred, crop), CR.crop_mask(ops, gt, crop)
+        valid_p = cp if valid_p is None else valid_p * cp
+        valid_g = cg if valid_g is None else valid_g * cg
     d_pred = nn_distance(ops, pred, gt, max_dist, cell=cell)
     d_gt = nn_distance(ops, gt, pred, max_dist, cell=cell)
     sp, sg = side_stats(ops, d_pred, valid_p, max_dist, thresholds), side_stats(ops, d_gt, valid_g, max_dist, thresholds)
@@ -285,6 +307,10 @@ def evaluate(ops: Ops, pred, gt, max_dist: float, thresholds, density: float | N
            "thresholds": thresholds, "precision": precision, "recall": recall,
            "fscore": [2 * p * r / (p + r) if p + r > 0 else 0.0 for p, r in zip(precision, recall)],
            "density": density, "pred_points_read": n_pred_in, "pred": sp, "gt": sg}
+    if transform is not None:
+        res["transformation"] = transform.tolist()
+    if reg is not None:
+        res["registration"] = reg
     if return_distances:
         res["_distances"] = (pred, d_pred, gt, d_gt, kept)
     return res
@@ -297,9 +323,11 @@ def error_colours(dist: torch.Tensor, max_dist: float) -> np.ndarray:
     return (rgb * 255 + 0.5).astype(np.uint8)
 
 
-def evaluate_files(ops: Ops, pred_ply: str, gt_ply: str, max_dist: float, thresholds, density=None, roi=None, error_ply=None) -> dict:
+def evaluate_files(ops: Ops, pred_ply: str, gt_ply: str, max_dist: float, thresholds, density=None, roi=None, error_ply=None, transform=None, crop=None,
+                   register=None) -> dict:
     pred, gt = IO.read_ply(pred_ply)[0], IO.read_ply(gt_ply)[0]
-    res = evaluate(ops, pred, gt, max_dist, thresholds, density=density, roi=roi, return_distances=error_ply is not None)
+    res = evaluate(ops, pred, gt, max_dist, thresholds, density=density, roi=roi, return_distances=error_ply is not None, transform=transform, crop=crop,
+                   register=register)
     if error_ply is not None:
         p, d = res.pop("_distances")[:2]
         IO.write_ply(error_ply, p.cpu().numpy(), error_colours(d, max_dist))
@@ -317,6 +345,12 @@ def main(argv=None):
     ap.add_argument("--dtu_plane", default=None, help="DTU Plane<scan>.mat (needs scipy)")
     ap.add_argument("--roi", default=None, help="an ROI saved with numpy.savez(mask=, origin=, resolution=[, plane=])")
     ap.add_argument("--error_ply", default=None, help="write the (thinned) prediction coloured by its clamped distance")
+    ap.add_argument("--transform", default=None, help="4x4 text file: moves the prediction into the ground truth's frame first")
+    ap.add_argument("--crop", default=None, help="crop volume .json (Tanks&Temples): points outside it are left out of the scores")
+    ap.add_argument("--register", type=float, default=None, metavar="MAX_CORR", help="refine the transform by ICP with this correspondence distance first")
+    ap.add_argument("--register_voxel", type=float, default=None, help="--register: thin both clouds to this voxel size for the ICP")
+    ap.add_argument("--register_max_iter", type=int, default=30)
+    ap.add_argument("--register_with_scale", action="store_true", help="--register: estimate a scale as well")
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
     if a.roi and (a.dtu_obs_mask or a.dtu_plane):
@@ -324,7 +358,12 @@ def main(argv=None):
     if a.dtu_plane and not a.dtu_obs_mask:
         raise SystemExit("--dtu_plane needs --dtu_obs_mask")
     roi = load_roi(a.roi) if a.roi else (load_dtu_roi(a.dtu_obs_mask, a.dtu_plane) if a.dtu_obs_mask else None)
-    res = evaluate_files(Ops.for_device(a.device), a.pred, a.gt, a.max_dist, a.thresholds, density=a.density, roi=roi, error_ply=a.error_ply)
+    extra = {}
+    if a.transform or a.crop or a.register is not None:
+        from . import cloud_register as CR
+        extra = {"transform": CR.load_transform(a.transform) if a.transform else None, "crop": CR.load_crop_json(a.crop) if a.crop else None,
+                 "register": None if a.register is None else {"schedule": [(a.register_voxel, a.register, a.register_max_iter)], "with_scale": a.register_with_scale}}
+    res = evaluate_files(Ops.for_device(a.device), a.pred, a.gt, a.max_dist, a.thresholds, density=a.density, roi=roi, error_ply=a.error_ply, **extra)
     print(json.dumps(res), flush=True)
     return res
 

@@ -22,146 +22,9 @@
 // dmvs_cloud_stats_f32: counts and the fixed-point sum of the distances.  Lanes accumulate u64 counters, waves reduce with shuffles, the
 // workgroup through LDS, then ONE integer atomicAdd per counter per workgroup: integer sums are associative, so every metric is bitwise
 // independent of launch order and grid shape (the rule of view_select.hip and the GroupNorm statistics).
-#include <math.h>
-#include "dmvs_common.h"
+#include "cloud_walk.h"      // the walk, shared with dmvs_cloud_nn_index_f32 (cloud_register.hip)
 
 namespace {
-
-struct CloudGrid {
-    const int64_t* keys;       // [C] occupied cells, ascending
-    const int64_t* start;      // [C + 1] first target of each cell
-    long C;
-    double ox, oy, oz, h;
-    int nx, ny, nz, bx, by;
-};
-
-// first index in [lo, hi) whose key is >= k (hi if none)
-__device__ __forceinline__ long cloud_lower_bound(const int64_t* __restrict__ keys, long lo, long hi, int64_t k) {
-    while (lo < hi) {
-        const long mid = (lo + hi) >> 1;
-        if (keys[mid] < k) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-// gap, in cells, between a query at offset t (cells, relative to its own cell's lower face) and the cell at integer offset d
-__device__ __forceinline__ double cloud_gap(int d, double t) { return fmax(0.0, fmax((double)d - t, t - (double)(d + 1))); }
-
-constexpr float kPruneMargin = 1.00001f;
-
-struct CloudQuery {
-    float qx, qy, qz;
-    double tx, ty, tz;          // position inside the (clamped) own cell, in cells
-    int cx, cy, cz;
-    float best2;
-    int points;                 // targets tested (the optional work output)
-};
-
-__device__ __forceinline__ void cloud_scan_cell(CloudQuery& q, const CloudGrid& g, const float* __restrict__ target, long c) {
-#pragma clang fp contract(off)
-    const long p0 = g.start[c], p1 = g.start[c + 1];
-    for (long p = p0; p < p1; ++p) {
-        const float dx = q.qx - target[3 * p], dy = q.qy - target[3 * p + 1], dz = q.qz - target[3 * p + 2];
-        const float d2 = (dx * dx + dy * dy) + dz * dz;
-        q.best2 = d2 < q.best2 ? d2 : q.best2;
-    }
-    q.points += (int)(p1 - p0);
-}
-
-// one occupied row (y, z): its cells outward from the query's x; g2yz = squared gap of the row (length units)
-__device__ __forceinline__ void cloud_visit_row(CloudQuery& q, const CloudGrid& g, const float* __restrict__ target, int y, int z, float g2yz) {
-    const int64_t row = ((int64_t)z << g.by) | y, base = row << g.bx;
-    const long cm = cloud_lower_bound(g.keys, 0, g.C, base | q.cx);
-    for (long c = cm; c < g.C; ++c) {                      // x >= cx
-        const int64_t k = g.keys[c];
-        if ((k >> g.bx) != row) break;
-        const float gx = (float)(cloud_gap((int)(k - base) - q.cx, q.tx) * g.h);
-        if (gx * gx + g2yz >= q.best2 * kPruneMargin) break;
-        cloud_scan_cell(q, g, target, c);
-    }
-    for (long c = cm - 1; c >= 0; --c) {                   // x < cx
-        const int64_t k = g.keys[c];
-        if ((k >> g.bx) != row) break;
-        const float gx = (float)(cloud_gap((int)(k - base) - q.cx, q.tx) * g.h);
-        if (gx * gx + g2yz >= q.best2 * kPruneMargin) break;
-        cloud_scan_cell(q, g, target, c);
-    }
-}
-
-// one slab z: its occupied rows outward from the query's y
-__device__ __forceinline__ void cloud_visit_slab(CloudQuery& q, const CloudGrid& g, const float* __restrict__ target, int z, float g2z) {
-    const int sh = g.bx + g.by;
-    const int64_t ymask = ((int64_t)1 << g.by) - 1;
-    for (int y = q.cy; y < g.ny;) {                        // rows >= cy: the first occupied row at or after y
-        const long c = cloud_lower_bound(g.keys, 0, g.C, (((int64_t)z << g.by) | y) << g.bx);
-        if (c >= g.C) break;
-        const int64_t k = g.keys[c];
-        if ((k >> sh) != z) break;
-        const int yo = (int)((k >> g.bx) & ymask);
-        const float gy = (float)(cloud_gap(yo - q.cy, q.ty) * g.h);
-        const float g2 = gy * gy + g2z;
-        if (g2 >= q.best2 * kPruneMargin) break;
-        cloud_visit_row(q, g, target, yo, z, g2);
-        y = yo + 1;
-    }
-    for (int y = q.cy - 1; y >= 0;) {                      // rows < cy: the last occupied row at or before y
-        const long c = cloud_lower_bound(g.keys, 0, g.C, (((int64_t)z << g.by) | (y + 1)) << g.bx) - 1;
-        if (c < 0) break;
-        const int64_t k = g.keys[c];
-        if ((k >> sh) != z) break;
-        const int yo = (int)((k >> g.bx) & ymask);
-        const float gy = (float)(cloud_gap(yo - q.cy, q.ty) * g.h);
-        const float g2 = gy * gy + g2z;
-        if (g2 >= q.best2 * kPruneMargin) break;
-        cloud_visit_row(q, g, target, yo, z, g2);
-        y = yo - 1;
-    }
-}
-
-__device__ __forceinline__ int cloud_clamp_cell(double u, int n) {
-    const double f = floor(u);
-    return f < 0.0 ? 0 : (f > (double)(n - 1) ? n - 1 : (int)f);      // (u is finite: checked by the caller)
-}
-
-__global__ void __launch_bounds__(DMVS_BLOCK)
-cloud_nn_dist_kernel(const float* __restrict__ query, long Q, const float* __restrict__ target, CloudGrid g, float max_dist,
-                     float* __restrict__ dist, int32_t* __restrict__ work) {
-    const long i = (long)blockIdx.x * DMVS_BLOCK + threadIdx.x;
-    if (i >= Q) return;
-    CloudQuery q;
-    q.qx = query[3 * i], q.qy = query[3 * i + 1], q.qz = query[3 * i + 2];
-    const double ux = ((double)q.qx - g.ox) / g.h, uy = ((double)q.qy - g.oy) / g.h, uz = ((double)q.qz - g.oz) / g.h;
-    int rings = 0;
-    q.points = 0;
-    q.best2 = max_dist * max_dist;
-    if (g.C > 0 && isfinite(ux) && isfinite(uy) && isfinite(uz)) {
-        q.cx = cloud_clamp_cell(ux, g.nx), q.cy = cloud_clamp_cell(uy, g.ny), q.cz = cloud_clamp_cell(uz, g.nz);
-        q.tx = ux - q.cx, q.ty = uy - q.cy, q.tz = uz - q.cz;
-        bool up = true, down = true;
-        for (int r = 0; up || down; ++r) {
-            rings = r + 1;
-            if (up) {
-                const int z = q.cz + r;
-                const float gz = (float)(cloud_gap(r, q.tz) * g.h);
-                if (z >= g.nz || gz * gz >= q.best2 * kPruneMargin) up = false;
-                else cloud_visit_slab(q, g, target, z, gz * gz);
-            }
-            if (r == 0) continue;
-            if (down) {
-                const int z = q.cz - r;
-                const float gz = (float)(cloud_gap(-r, q.tz) * g.h);
-                if (z < 0 || gz * gz >= q.best2 * kPruneMargin) down = false;
-                else cloud_visit_slab(q, g, target, z, gz * gz);
-            }
-        }
-    }
-    const float d = sqrtf(q.best2);
-    dist[i] = q.best2 < max_dist * max_dist ? fminf(d, max_dist) : max_dist;
-    if (work) {
-        work[2 * i] = rings;
-        work[2 * i + 1] = q.points;
-    }
-}
 
 #define CLOUD_MAX_T DMVS_CLOUD_MAX_THRESHOLDS
 #define CLOUD_NCOUNT (3 + CLOUD_MAX_T)
@@ -207,35 +70,20 @@ cloud_stats_kernel(const float* __restrict__ dist, const uint8_t* __restrict__ v
     }
 }
 
-int cloud_bits(long n) {
-    int b = 0;
-    while ((1L << b) < n) ++b;
-    return b;
-}
-
 }  // namespace
 
 extern "C" int dmvs_cloud_nn_dist_f32(const float* query, int64_t Q, const float* target, int64_t M, const int64_t* cell_keys,
                                       const int64_t* cell_start, int64_t C, const double* origin, double h, const int32_t* dims,
                                       float max_dist, float* dist, int32_t* work, void* stream) {
-    if (Q < 0 || M < 0 || C < 0 || C > M || !origin || !dims) return DMVS_EINVAL;
-    if (!(h > 0.0) || !isfinite(h) || !(max_dist > 0.0f) || !isfinite(max_dist)) return DMVS_EINVAL;
-    if (!isfinite(origin[0]) || !isfinite(origin[1]) || !isfinite(origin[2])) return DMVS_EINVAL;
     if (Q > 0 && (!query || !dist)) return DMVS_EINVAL;
-    if (M > 0 && (!target || !cell_keys || !cell_start || C < 1)) return DMVS_EINVAL;
-    if (M == 0 && C != 0) return DMVS_EINVAL;
-    if (dims[0] < 1 || dims[1] < 1 || dims[2] < 1) return DMVS_EINVAL;
-    if (ceil((double)max_dist / h) > (double)DMVS_CLOUD_MAX_RINGS) return DMVS_EINVAL;
     CloudGrid g;
-    g.bx = cloud_bits(dims[0]), g.by = cloud_bits(dims[1]);
-    if (g.bx + g.by + cloud_bits(dims[2]) > DMVS_CLOUD_MAX_KEY_BITS) return DMVS_EINVAL;      // the grid exceeds the key range
+    const int rc = cloud_grid_args(Q, M, target, cell_keys, cell_start, C, origin, h, dims, max_dist, g);
+    if (rc != 0) return rc;
     if (Q == 0) return 0;
-    g.keys = cell_keys, g.start = cell_start, g.C = (long)C;
-    g.ox = origin[0], g.oy = origin[1], g.oz = origin[2], g.h = h;
-    g.nx = dims[0], g.ny = dims[1], g.nz = dims[2];
-    if (dmvs_ceil_div(Q, DMVS_BLOCK) > (1u << 30) || Q > (1L << 38)) return DMVS_EINVAL;
     dim3 grid(dmvs_ceil_div(Q, DMVS_BLOCK)), block(DMVS_BLOCK);
-    hipLaunchKernelGGL(cloud_nn_dist_kernel, grid, block, 0, (hipStream_t)stream, query, (long)Q, target, g, max_dist, dist, work);
+    CloudTransform T;
+    cloud_transform_arg(nullptr, T);
+    hipLaunchKernelGGL(cloud_nn_kernel<false>, grid, block, 0, (hipStream_t)stream, query, (long)Q, target, g, max_dist, T, dist, (int32_t*)nullptr, work);
     return dmvs_launch_status();
 }
 

@@ -1,0 +1,219 @@
+// The grid walk of the point-cloud kernels, shared by dmvs_cloud_nn_dist_f32 (cloud_eval.hip) and dmvs_cloud_nn_index_f32
+// (cloud_register.hip); the walk itself is described at the top of cloud_eval.hip.  INDEX = true also tracks WHICH target is the
+// nearest (one more register and a select per target tested); with INDEX = false that member is never read and the walk compiles
+// to what it was before the index search existed.
+#pragma once
+#include <math.h>
+#include "dmvs_common.h"
+
+namespace {
+
+struct CloudGrid {
+    const int64_t* keys;       // [C] occupied cells, ascending
+    const int64_t* start;      // [C + 1] first target of each cell
+    long C;
+    double ox, oy, oz, h;
+    int nx, ny, nz, bx, by;
+};
+
+// an optional similarity applied to a point before anything else: p' = fp32(((m0 x + m1 y) + m2 z) + m3) per row, products and sums
+// in fp64 in exactly this order without contraction, ONE rounding to fp32 (include/dmvs.h)
+struct CloudTransform {
+    double m[12];              // row-major 3x4 [sR | t]
+    int on;                    // 0: identity (the point is taken as it is)
+};
+
+__device__ __forceinline__ void cloud_move(const CloudTransform& T, float& x, float& y, float& z) {
+#pragma clang fp contract(off)
+    if (!T.on) return;
+    const double dx = x, dy = y, dz = z;
+    x = (float)(((T.m[0] * dx + T.m[1] * dy) + T.m[2] * dz) + T.m[3]);
+    y = (float)(((T.m[4] * dx + T.m[5] * dy) + T.m[6] * dz) + T.m[7]);
+    z = (float)(((T.m[8] * dx + T.m[9] * dy) + T.m[10] * dz) + T.m[11]);
+}
+
+// the fp32 squared distance of the searches: three differences, three products, two sums, no contraction
+__device__ __forceinline__ float cloud_dist2(float qx, float qy, float qz, const float* __restrict__ t) {
+#pragma clang fp contract(off)
+    const float dx = qx - t[0], dy = qy - t[1], dz = qz - t[2];
+    return (dx * dx + dy * dy) + dz * dz;
+}
+
+// first index in [lo, hi) whose key is >= k (hi if none)
+__device__ __forceinline__ long cloud_lower_bound(const int64_t* __restrict__ keys, long lo, long hi, int64_t k) {
+    while (lo < hi) {
+        const long mid = (lo + hi) >> 1;
+        if (keys[mid] < k) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// gap, in cells, between a query at offset t (cells, relative to its own cell's lower face) and the cell at integer offset d
+__device__ __forceinline__ double cloud_gap(int d, double t) { return fmax(0.0, fmax((double)d - t, t - (double)(d + 1))); }
+
+constexpr float kPruneMargin = 1.00001f;
+
+struct CloudQuery {
+    float qx, qy, qz;
+    double tx, ty, tz;          // position inside the (clamped) own cell, in cells
+    int cx, cy, cz;
+    float best2;
+    int best_i;                 // INDEX: the target that gave best2 (-1: none yet)
+    int points;                 // targets tested (the optional work output)
+};
+
+template <bool INDEX>
+__device__ __forceinline__ void cloud_scan_cell(CloudQuery& q, const CloudGrid& g, const float* __restrict__ target, long c) {
+#pragma clang fp contract(off)
+    const long p0 = g.start[c], p1 = g.start[c + 1];
+    for (long p = p0; p < p1; ++p) {
+        const float dx = q.qx - target[3 * p], dy = q.qy - target[3 * p + 1], dz = q.qz - target[3 * p + 2];
+        const float d2 = (dx * dx + dy * dy) + dz * dz;
+        if (INDEX) q.best_i = d2 < q.best2 ? (int)p : q.best_i;      // (strict: the first of exactly equidistant targets in walk order stays)
+        q.best2 = d2 < q.best2 ? d2 : q.best2;
+    }
+    q.points += (int)(p1 - p0);
+}
+
+// one occupied row (y, z): its cells outward from the query's x; g2yz = squared gap of the row (length units)
+template <bool INDEX>
+__device__ __forceinline__ void cloud_visit_row(CloudQuery& q, const CloudGrid& g, const float* __restrict__ target, int y, int z, float g2yz) {
+    const int64_t row = ((int64_t)z << g.by) | y, base = row << g.bx;
+    const long cm = cloud_lower_bound(g.keys, 0, g.C, base | q.cx);
+    for (long c = cm; c < g.C; ++c) {                      // x >= cx
+        const int64_t k = g.keys[c];
+        if ((k >> g.bx) != row) break;
+        const float gx = (float)(cloud_gap((int)(k - base) - q.cx, q.tx) * g.h);
+        if (gx * gx + g2yz >= q.best2 * kPruneMargin) break;
+        cloud_scan_cell<INDEX>(q, g, target, c);
+    }
+    for (long c = cm - 1; c >= 0; --c) {                   // x < cx
+        const int64_t k = g.keys[c];
+        if ((k >> g.bx) != row) break;
+        const float gx = (float)(cloud_gap((int)(k - base) - q.cx, q.tx) * g.h);
+        if (gx * gx + g2yz >= q.best2 * kPruneMargin) break;
+        cloud_scan_cell<INDEX>(q, g, target, c);
+    }
+}
+
+// one slab z: its occupied rows outward from the query's y
+template <bool INDEX>
+__device__ __forceinline__ void cloud_visit_slab(CloudQuery& q, const CloudGrid& g, const float* __restrict__ target, int z, float g2z) {
+    const int sh = g.bx + g.by;
+    const int64_t ymask = ((int64_t)1 << g.by) - 1;
+    for (int y = q.cy; y < g.ny;) {                        // rows >= cy: the first occupied row at or after y
+        const long c = cloud_lower_bound(g.keys, 0, g.C, (((int64_t)z << g.by) | y) << g.bx);
+        if (c >= g.C) break;
+        const int64_t k = g.keys[c];
+        if ((k >> sh) != z) break;
+        const int yo = (int)((k >> g.bx) & ymask);
+        const float gy = (float)(cloud_gap(yo - q.cy, q.ty) * g.h);
+        const float g2 = gy * gy + g2z;
+        if (g2 >= q.best2 * kPruneMargin) break;
+        cloud_visit_row<INDEX>(q, g, target, yo, z, g2);
+        y = yo + 1;
+    }
+    for (int y = q.cy - 1; y >= 0;) {                      // rows < cy: the last occupied row at or before y
+        const long c = cloud_lower_bound(g.keys, 0, g.C, (((int64_t)z << g.by) | (y + 1)) << g.bx) - 1;
+        if (c < 0) break;
+        const int64_t k = g.keys[c];
+        if ((k >> sh) != z) break;
+        const int yo = (int)((k >> g.bx) & ymask);
+        const float gy = (float)(cloud_gap(yo - q.cy, q.ty) * g.h);
+        const float g2 = gy * gy + g2z;
+        if (g2 >= q.best2 * kPruneMargin) break;
+        cloud_visit_row<INDEX>(q, g, target, yo, z, g2);
+        y = yo - 1;
+    }
+}
+
+__device__ __forceinline__ int cloud_clamp_cell(double u, int n) {
+    const double f = floor(u);
+    return f < 0.0 ? 0 : (f > (double)(n - 1) ? n - 1 : (int)f);      // (u is finite: checked by the caller)
+}
+
+// the search of one query: moves it (T), walks the grid, writes dist (may be NULL with INDEX) / index (INDEX only) / work (may be NULL)
+template <bool INDEX>
+__global__ void __launch_bounds__(DMVS_BLOCK)
+cloud_nn_kernel(const float* __restrict__ query, long Q, const float* __restrict__ target, CloudGrid g, float max_dist, CloudTransform T,
+                float* __restrict__ dist, int32_t* __restrict__ index, int32_t* __restrict__ work) {
+    const long i = (long)blockIdx.x * DMVS_BLOCK + threadIdx.x;
+    if (i >= Q) return;
+    CloudQuery q;
+    q.qx = query[3 * i], q.qy = query[3 * i + 1], q.qz = query[3 * i + 2];
+    if (INDEX) cloud_move(T, q.qx, q.qy, q.qz);
+    const double ux = ((double)q.qx - g.ox) / g.h, uy = ((double)q.qy - g.oy) / g.h, uz = ((double)q.qz - g.oz) / g.h;
+    int rings = 0;
+    q.points = 0;
+    q.best_i = -1;
+    q.best2 = max_dist * max_dist;
+    if (g.C > 0 && isfinite(ux) && isfinite(uy) && isfinite(uz)) {
+        q.cx = cloud_clamp_cell(ux, g.nx), q.cy = cloud_clamp_cell(uy, g.ny), q.cz = cloud_clamp_cell(uz, g.nz);
+        q.tx = ux - q.cx, q.ty = uy - q.cy, q.tz = uz - q.cz;
+        bool up = true, down = true;
+        for (int r = 0; up || down; ++r) {
+            rings = r + 1;
+            if (up) {
+                const int z = q.cz + r;
+                const float gz = (float)(cloud_gap(r, q.tz) * g.h);
+                if (z >= g.nz || gz * gz >= q.best2 * kPruneMargin) up = false;
+                else cloud_visit_slab<INDEX>(q, g, target, z, gz * gz);
+            }
+            if (r == 0) continue;
+            if (down) {
+                const int z = q.cz - r;
+                const float gz = (float)(cloud_gap(-r, q.tz) * g.h);
+                if (z < 0 || gz * gz >= q.best2 * kPruneMargin) down = false;
+                else cloud_visit_slab<INDEX>(q, g, target, z, gz * gz);
+            }
+        }
+    }
+    const float d = q.best2 < max_dist * max_dist ? fminf(sqrtf(q.best2), max_dist) : max_dist;
+    if (INDEX) {
+        if (dist) dist[i] = d;
+        index[i] = d < max_dist ? q.best_i : -1;      // -1 exactly where the distance is the clamp
+    } else {
+        dist[i] = d;
+    }
+    if (work) {
+        work[2 * i] = rings;
+        work[2 * i + 1] = q.points;
+    }
+}
+
+inline int cloud_bits(long n) {
+    int b = 0;
+    while ((1L << b) < n) ++b;
+    return b;
+}
+
+// host-side validation and set-up of the grid operands the two searches share; 0 or DMVS_EINVAL
+inline int cloud_grid_args(int64_t Q, int64_t M, const float* target, const int64_t* cell_keys, const int64_t* cell_start, int64_t C,
+                           const double* origin, double h, const int32_t* dims, float max_dist, CloudGrid& g) {
+    if (Q < 0 || M < 0 || C < 0 || C > M || !origin || !dims) return DMVS_EINVAL;
+    if (!(h > 0.0) || !isfinite(h) || !(max_dist > 0.0f) || !isfinite(max_dist)) return DMVS_EINVAL;
+    if (!isfinite(origin[0]) || !isfinite(origin[1]) || !isfinite(origin[2])) return DMVS_EINVAL;
+    if (M > 0 && (!target || !cell_keys || !cell_start || C < 1)) return DMVS_EINVAL;
+    if (M == 0 && C != 0) return DMVS_EINVAL;
+    if (dims[0] < 1 || dims[1] < 1 || dims[2] < 1) return DMVS_EINVAL;
+    if (ceil((double)max_dist / h) > (double)DMVS_CLOUD_MAX_RINGS) return DMVS_EINVAL;
+    g.bx = cloud_bits(dims[0]), g.by = cloud_bits(dims[1]);
+    if (g.bx + g.by + cloud_bits(dims[2]) > DMVS_CLOUD_MAX_KEY_BITS) return DMVS_EINVAL;      // the grid exceeds the key range
+    if (dmvs_ceil_div(Q, DMVS_BLOCK) > (1u << 30) || Q > (1L << 38)) return DMVS_EINVAL;
+    g.keys = cell_keys, g.start = cell_start, g.C = (long)C;
+    g.ox = origin[0], g.oy = origin[1], g.oz = origin[2], g.h = h;
+    g.nx = dims[0], g.ny = dims[1], g.nz = dims[2];
+    return 0;
+}
+
+// a HOST 3x4 row-major [sR | t] (NULL = identity) -> the kernel argument; DMVS_EINVAL for a non-finite entry
+inline int cloud_transform_arg(const double* transform, CloudTransform& T) {
+    T.on = transform ? 1 : 0;
+    for (int k = 0; k < 12; ++k) {
+        T.m[k] = transform ? transform[k] : (k % 5 == 0 ? 1.0 : 0.0);
+        if (!isfinite(T.m[k])) return DMVS_EINVAL;
+    }
+    return 0;
+}
+
+}  // namespace

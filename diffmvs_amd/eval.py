@@ -127,6 +127,8 @@ def main(argv=None):
     ap.add_argument("--photo_thres", type=float, nargs="+", default=[0.3, 0.0, 0.0], help="confidence threshold per stage")
     ap.add_argument("--gt_ply", default=None, help="with --filter: score every fused cloud against this ground-truth PLY ('{scene}' is substituted) "
                     "with diffmvs_amd.cloud_eval; adds cloud_metrics[scene] to the result")
+    ap.add_argument("--gt_transform", default=None, help="--gt_ply: 4x4 text file that moves the fused cloud into the ground truth's frame ('{scene}' is substituted)")
+    ap.add_argument("--gt_crop", default=None, help="--gt_ply: crop volume .json; points outside it are left out of the scores ('{scene}' is substituted)")
     ap.add_argument("--cloud_max_dist", type=float, default=20.0, help="--gt_ply: distances are clamped here (DTU: 20)")
     ap.add_argument("--cloud_density", type=float, default=None, help="--gt_ply: thin the fused cloud to one point per voxel of this side (DTU: 0.2)")
     ap.add_argument("--cloud_thresholds", type=float, nargs="*", default=[1.0, 2.0, 5.0], help="--gt_ply: F-score thresholds")
@@ -182,10 +184,15 @@ def main(argv=None):
             res.setdefault("ply", {})[scene] = kw["plyfilename"]
             if a.gt_ply:
                 from . import cloud_eval
+                extra = {}
+                if a.gt_transform or a.gt_crop:
+                    from . import cloud_register
+                    extra = {"transform": cloud_register.load_transform(a.gt_transform.replace("{scene}", scene)) if a.gt_transform else None,
+                             "crop": cloud_register.load_crop_json(a.gt_crop.replace("{scene}", scene)) if a.gt_crop else None}
                 from .ops import Ops
                 res.setdefault("cloud_metrics", {})[scene] = cloud_eval.evaluate_files(
                     Ops.for_device(device), kw["plyfilename"], a.gt_ply.replace("{scene}", scene), a.cloud_max_dist, a.cloud_thresholds,
-                    density=a.cloud_density)
+                    density=a.cloud_density, **extra)
     print(json.dumps(res), flush=True)
     return res
 

@@ -811,3 +811,64 @@ class Ops:
         self._call("dmvs_cloud_stats_f32", _ptr(dist), _ptr(valid), dist.numel(), float(max_dist), thr, T, float(scale), int(blocks),
                    _ptr(out), self.stream())
         return out
+
+    # ------------------------------------------------------------------ registration and cropping (diffmvs_amd/cloud_register.py)
+    @staticmethod
+    def _transform_arg(transform):
+        """None or anything shaped [3,4] / [4,4] -> a host array of 12 doubles (row-major [sR | t]) or None"""
+        if transform is None:
+            return None
+        import numpy as np
+        m = np.asarray(transform.detach().cpu().numpy() if torch.is_tensor(transform) else transform, np.float64)
+        if m.shape not in ((3, 4), (4, 4)):
+            raise _lib.DmvsError(f"a transform is a 3x4 or 4x4 matrix, got {m.shape}")
+        return (C.c_double * 12)(*[float(v) for v in m[:3].reshape(-1)])
+
+    def cloud_nn_index(self, query, target, cell_keys, cell_start, origin, h, dims, max_dist, transform=None, dist=True, work=False):
+        """dmvs_cloud_nn_index_f32: cloud_nn_dist on the query moved by `transform`, plus the position of the nearest target in the
+        sorted target array (-1 where nothing is closer than max_dist).  -> (dist [Q] fp32 or None, index [Q] int32[, work [Q,2]])."""
+        self._chk_typed("cloud_nn_index", (query, torch.float32), (target, torch.float32), (cell_keys, torch.int64), (cell_start, torch.int64))
+        Q, M, Cn = int(query.shape[0]), int(target.shape[0]), int(cell_keys.numel())
+        if query.dim() != 2 or query.shape[1] != 3 or target.dim() != 2 or target.shape[1] != 3:
+            raise _lib.DmvsError("cloud_nn_index: query and target must be [N,3]")
+        if cell_start.numel() != Cn + 1 or Cn > M or (M > 0 and Cn < 1):
+            raise _lib.DmvsError("cloud_nn_index: cell_start must have one entry more than cell_keys, and every target a cell")
+        d = self.empty(Q) if dist else None
+        index = torch.empty(Q, dtype=torch.int32, device=self.device)
+        wk = torch.empty(Q, 2, dtype=torch.int32, device=self.device) if work else None
+        o = (C.c_double * 3)(*[float(v) for v in origin])
+        dm = (C.c_int32 * 3)(*[int(v) for v in dims])
+        self._call("dmvs_cloud_nn_index_f32", _ptr(query), Q, _ptr(target), M, _ptr(cell_keys), _ptr(cell_start), Cn, o, float(h), dm,
+                   float(max_dist), self._transform_arg(transform), _ptr(d), _ptr(index), _ptr(wk), self.stream())
+        return (d, index, wk) if work else (d, index)
+
+    def cloud_pair_moments(self, source, transform, target, index, valid, max_corr, center_p, center_q, bound, scale_linear, scale_quadratic,
+                           blocks=0):
+        """dmvs_cloud_pair_moments_f64 -> [20] int64 on the device: the fixed-point sums of one ICP step (include/dmvs.h)"""
+        self._chk_typed("cloud_pair_moments", (source, torch.float32), (target, torch.float32), (index, torch.int32), (valid, torch.uint8))
+        N = int(source.shape[0])
+        if source.dim() != 2 or source.shape[1] != 3 or target.dim() != 2 or target.shape[1] != 3:
+            raise _lib.DmvsError("cloud_pair_moments: source and target must be [N,3]")
+        if index.numel() != N or (valid is not None and valid.numel() != N):
+            raise _lib.DmvsError("cloud_pair_moments: index (and the validity mask) must have one entry per source point")
+        out = torch.empty(_lib.CLOUD_MOMENTS, dtype=torch.int64, device=self.device)
+        cp = (C.c_double * 3)(*[float(v) for v in center_p])
+        cq = (C.c_double * 3)(*[float(v) for v in center_q])
+        self._call("dmvs_cloud_pair_moments_f64", _ptr(source), N, self._transform_arg(transform), _ptr(target), int(target.shape[0]), _ptr(index),
+                   _ptr(valid), float(max_corr), cp, cq, float(bound), float(scale_linear), float(scale_quadratic), int(blocks), _ptr(out),
+                   self.stream())
+        return out
+
+    def cloud_crop_prism(self, points, polygon, axis, axis_min, axis_max, transform=None):
+        """dmvs_cloud_crop_prism_f32 -> uint8 [N]: 1 where the (moved) point lies inside the polygon prism.  polygon [K,2] fp64 on this
+        binding's device, axis 0 / 1 / 2 (include/dmvs.h)."""
+        self._chk_typed("cloud_crop_prism", (points, torch.float32), (polygon, torch.float64))
+        if points.dim() != 2 or points.shape[1] != 3 or polygon.dim() != 2 or polygon.shape[1] != 2:
+            raise _lib.DmvsError("cloud_crop_prism: points must be [N,3] and the polygon [K,2]")
+        K = int(polygon.shape[0])
+        if not 3 <= K <= _lib.CLOUD_MAX_POLYGON:
+            raise _lib.DmvsError(f"cloud_crop_prism: a polygon of {K} vertices; 3..{_lib.CLOUD_MAX_POLYGON} are supported")
+        out = torch.empty(points.shape[0], dtype=torch.uint8, device=self.device)
+        self._call("dmvs_cloud_crop_prism_f32", _ptr(points), int(points.shape[0]), self._transform_arg(transform), _ptr(polygon), K, int(axis),
+                   float(axis_min), float(axis_max), _ptr(out), self.stream())
+        return out

@@ -526,6 +526,55 @@ int dmvs_cloud_nn_dist_f32(const float* query, int64_t Q, const float* target, i
 int dmvs_cloud_stats_f32(const float* dist, const uint8_t* valid, int64_t N, float max_dist, const float* thresholds, int32_t T,
                          double scale, int32_t blocks, uint64_t* out, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Point-cloud registration and cropping (added under ABI 4, additive; diffmvs_amd/cloud_register.py runs ICP on them).
+ *
+ * `transform` (all three): a HOST pointer to a row-major 3x4 [sR | t], NULL = identity.  The moved point is
+ *   p' = fp32(((m0 x + m1 y) + m2 z) + m3) per row: products and sums in fp64 in this order, no contraction, ONE rounding to fp32.
+ *
+ * dmvs_cloud_nn_index_f32: dmvs_cloud_nn_dist_f32 (same grid operands, same walk) that moves the query first and also says WHICH target
+ *   is the nearest.  dist: NULL or [Q] fp32, bit-identical to dmvs_cloud_nn_dist_f32 called on q', for any cell size.
+ *   index [Q] int32: the position in the SORTED target array of a target at distance dist[i] -- dist[i] is, bit for bit, the fp32
+ *   distance (same operation order) between q'_i and target[index[i]] -- or -1 where dist[i] == max_dist (nothing closer than max_dist).
+ *   Between exactly equidistant targets (equal fp32 squared distances) ANY one of them may be returned: which one depends on the walk
+ *   order, hence on the cell size.  work as in dmvs_cloud_nn_dist_f32.
+ *   DMVS_EINVAL: as dmvs_cloud_nn_dist_f32 (dist may be NULL, index may not), M >= 2^31, a non-finite transform entry.
+ *
+ * dmvs_cloud_pair_moments_f64: the sums one ICP step needs, over the pairs (source_i moved by `transform`, target[index[i]]).
+ *   source [N,3] fp32;  target [M,3] fp32 (the sorted array `index` refers to);  index [N] int32;  valid: NULL (all) or [N] uint8.
+ *   A pair is counted when index[i] >= 0, valid allows it, and the fp32 distance |q' - target| (the search's operation order) is <= max_corr.
+ *   center_p, center_q: HOST, 3 doubles each.  With p = (double)q' - center_p, t = (double)target - center_q, out [DMVS_CLOUD_MOMENTS]
+ *   int64 (device, zeroed here) =
+ *     [0] pairs   [1..3] sum p   [4..6] sum t   [7..15] sum p_a t_b (row-major a, b)   [16] sum |p|^2   [17] sum |t|^2
+ *     [18] sum |(double)q' - (double)target|^2   [19] pairs NOT summed because a |p_k| or |t_k| exceeded `bound` or index[i] >= M
+ *   [1..6] are sums of rint(value * scale_linear), [7..18] of rint(value * scale_quadratic), signed 64-bit in two's complement; a sum of
+ *   n terms is within n * 0.5 / scale of the exact sum.  Integer adds (lanes, wave shuffles, LDS, one atomic per counter per workgroup):
+ *   bitwise independent of the launch shape, of `blocks` (0 = the library's choice) and of the order of the points.
+ *   Resolution: centring bounds the coordinates by the clouds' half-extent B instead of their distance from the origin; the caller takes
+ *   the largest powers of two with N B scale_linear < 2^62 and N max(3 B^2, max_corr^2) scale_quadratic < 2^62.  N = 10^7, B = 500 (a
+ *   DTU scan centred on its box): scale_quadratic = 2^19, so the quadratic sums (order N B^2 / 3 ~ 10^12) carry at most 10 units
+ *   (1e-11 relative) of rounding and the linear sums (2^29) at most 0.01 unit.
+ *   DMVS_EINVAL: NULL operands, N or M < 0, M >= 2^31, max_corr / bound not finite or <= 0, non-finite centres or transform, a scale
+ *   that is not a power of two, or one with N bound scale_linear >= 2^62 or N max(3 bound^2, (1.001 max_corr)^2) scale_quadratic >= 2^62.
+ *
+ * dmvs_cloud_crop_prism_f32: inside [N] uint8 = 1 where the (moved) point lies in the prism, the crop volume of a Tanks&Temples scene.
+ *   polygon: DEVICE [K,2] fp64 (u, v) vertices, 3 <= K <= DMVS_CLOUD_MAX_POLYGON;  axis 0 / 1 / 2 = X / Y / Z: (u, v, w) = (1,2,0) /
+ *   (0,2,1) / (0,1,2).  Inside: axis_min <= w <= axis_max (both ends included; infinite ends allowed) and (u, v) inside the polygon by the
+ *   even-odd rule: edge (i, j = i - 1 cyclic) toggles when (v_i > v) != (v_j > v) and u < (u_j - u_i) * (v - v_i) / (v_j - v_i) + u_i,
+ *   all in fp64 on the point's fp32 coordinates, in exactly this operation order, no contraction.  The mask is a `valid` of dmvs_cloud_stats_f32.
+ *   DMVS_EINVAL: NULL operands, N < 0, K outside [3, DMVS_CLOUD_MAX_POLYGON], axis outside [0, 2], axis_min > axis_max or NaN, a non-finite transform. */
+#define DMVS_CLOUD_MOMENTS 20
+#define DMVS_CLOUD_MAX_POLYGON 256
+int dmvs_cloud_nn_index_f32(const float* query, int64_t Q, const float* target, int64_t M, const int64_t* cell_keys,
+                            const int64_t* cell_start, int64_t C, const double* origin, double h, const int32_t* dims,
+                            float max_dist, const double* transform, float* dist, int32_t* index, int32_t* work, void* stream);
+int dmvs_cloud_pair_moments_f64(const float* source, int64_t N, const double* transform, const float* target, int64_t M,
+                                const int32_t* index, const uint8_t* valid, float max_corr, const double* center_p,
+                                const double* center_q, double bound, double scale_linear, double scale_quadratic, int32_t blocks,
+                                int64_t* out, void* stream);
+int dmvs_cloud_crop_prism_f32(const float* points, int64_t N, const double* transform, const double* polygon, int32_t K,
+                              int32_t axis, double axis_min, double axis_max, uint8_t* inside, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
