@@ -11,7 +11,7 @@ fscore = 2 P R / (P + R)).  Both are two nearest-neighbour searches between the 
 walks.  Clouds that do not share a frame and a region of interest yet are aligned and cropped first: --transform T.txt (a 4x4
 alignment), --register MAX_CORR (ICP refinement of it on the GPU) and --crop crop.json (a Tanks&Temples crop volume) -- see
 diffmvs_amd.cloud_register.  The official MATLAB / Tanks&Temples tools remain the authority for published numbers:
-`voxel_downsample` below is NOT the DTU scorer's thinning (see its docstring)."""
+`voxel_downsample` (diffmvs_amd.cloud_grid) is NOT the DTU scorer's thinning (see its docstring)."""
 from __future__ import annotations
 
 import argparse
@@ -22,97 +22,27 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import cloud_register as CR
 from . import formats as IO
+from .cloud_grid import FAR_RINGS, NEAR_RINGS, build_grid, estimate_spacing, order_by_grid, pow2_scale_below, to_cloud, voxel_downsample  # noqa: F401
 from .ops import Ops
 
-NEAR_RINGS = 4      # nn_distance: the fine pass searches this many cells far ...
-FAR_RINGS = 8       # ... the coarse pass covers max_dist in this many
 
-
-# ------------------------------------------------------------------------------------------ grid
-def _bits(n: int) -> int:
-    return max(0, int(n) - 1).bit_length()
-
-
-def _cells(xyz: torch.Tensor, origin, h: float) -> torch.Tensor:
-    """integer cell coordinates floor((p - origin) / h) in fp64: the arithmetic the kernel repeats for its queries"""
-    o = torch.tensor(list(origin), dtype=torch.float64, device=xyz.device)
-    return torch.floor((xyz.double() - o) / float(h)).long()
-
-
-def _key(cells: torch.Tensor, dims) -> torch.Tensor:
-    bx, by = _bits(dims[0]), _bits(dims[1])
-    return (cells[:, 2] << (bx + by)) | (cells[:, 1] << bx) | cells[:, 0]
-
-
-def build_grid(target: torch.Tensor, cell: float) -> dict:
-    """sort `target` [M,3] fp32 into a uniform grid of cell side `cell` whose origin is the cloud's minimum corner.
-    -> {target (sorted), keys [C], start [C+1], origin, dims, cell}: the operands of Ops.cloud_nn_dist"""
-    if not (cell > 0 and math.isfinite(cell)):
-        raise ValueError(f"cell size must be positive and finite, got {cell}")
-    dev = target.device
-    if target.shape[0] == 0:
-        z = torch.zeros(0, dtype=torch.int64, device=dev)
-        return {"target": target.reshape(0, 3).contiguous(), "keys": z, "start": torch.zeros(1, dtype=torch.int64, device=dev),
-                "origin": (0.0, 0.0, 0.0), "dims": (1, 1, 1), "cell": float(cell)}
-    if not bool(torch.isfinite(target).all()):
-        raise ValueError("the target cloud holds non-finite coordinates")
-    lo = target.min(0).values.double()
-    origin = tuple(float(v) for v in lo.cpu())
-    cells = _cells(target, origin, cell)
-    dims = tuple(int(v) + 1 for v in cells.max(0).values.cpu())
-    if sum(_bits(n) for n in dims) > _lib.CLOUD_MAX_KEY_BITS:
-        raise ValueError(f"a grid of {dims} cells of side {cell} exceeds the {_lib.CLOUD_MAX_KEY_BITS}-bit key: raise the cell size")
-    key, order = torch.sort(_key(cells, dims))
-    keys, counts = torch.unique_consecutive(key, return_counts=True)
-    start = torch.zeros(keys.numel() + 1, dtype=torch.int64, device=dev)
-    torch.cumsum(counts, 0, out=start[1:])
-    return {"target": target[order].contiguous(), "keys": keys, "start": start, "origin": origin, "dims": dims, "cell": float(cell)}
-
-
+# ------------------------------------------------------------------------------------------ search
 def grid_nn(ops: Ops, query: torch.Tensor, grid: dict, max_dist: float, work: bool = False):
     """one launch of the kernel on a built grid: the queries are sorted by the grid's key first (neighbouring lanes then read the
     same cells) and the results scattered back.  -> dist [Q] fp32 (and work [Q,2] int32 with work=True)"""
-    Q = query.shape[0]
-    if Q and grid["keys"].numel():
-        dims = grid["dims"]
-        hi = torch.tensor([n - 1 for n in dims], device=query.device)
-        c = _cells(torch.nan_to_num(query, nan=0.0, posinf=3e38, neginf=-3e38), grid["origin"], grid["cell"])
-        order = torch.sort(_key(torch.minimum(c.clamp_min_(0), hi), dims)).indices
-        q = query[order].contiguous()
-    else:
-        order, q = None, query.contiguous()
+    order = order_by_grid(query, grid)
+    q = query.contiguous() if order is None else query[order].contiguous()
     res = ops.cloud_nn_dist(q, grid["target"], grid["keys"], grid["start"], grid["origin"], grid["cell"], grid["dims"], max_dist, work=work)
     if order is None:
         return res
-    d, wk = res if work else (res, None)
-    out = torch.empty_like(d)
-    out[order] = d
-    if not work:
+
+    def unsort(r):
+        out = torch.empty_like(r)
+        out[order] = r
         return out
-    wout = torch.empty_like(wk)
-    wout[order] = wk
-    return out, wout
-
-
-def estimate_spacing(points: torch.Tensor, probe: float) -> float:
-    """typical distance between neighbouring points of a SURFACE sample: with n points in an occupied probe cell of side s, a
-    surface patch of area ~ s^2 holds them at spacing s / sqrt(n)"""
-    if points.shape[0] < 2:
-        return float(probe)
-    lo = points.min(0).values.double()
-    c = torch.floor((points.double() - lo) / probe).long()
-    c = c - c.min(0).values
-    ny, nz = int(c[:, 1].max()) + 1, int(c[:, 2].max()) + 1
-    occupied = torch.unique((c[:, 0] * ny + c[:, 1]) * nz + c[:, 2]).numel()
-    return float(probe / math.sqrt(max(1.0, points.shape[0] / occupied)))
-
-
-def _to_cloud(ops: Ops, x) -> torch.Tensor:
-    t = torch.as_tensor(np.ascontiguousarray(x) if isinstance(x, np.ndarray) else x)
-    if t.dim() != 2 or t.shape[1] != 3:
-        raise ValueError(f"a cloud is an [N,3] array, got {tuple(t.shape)}")
-    return t.to(device=ops.device, dtype=torch.float32).contiguous()
+    return (unsort(res[0]), unsort(res[1])) if work else unsort(res)
 
 
 def nn_distance(ops: Ops, query, target, max_dist: float, cell: float | None = None, passes: int = 2, stats: dict | None = None) -> torch.Tensor:
@@ -128,7 +58,7 @@ def nn_distance(ops: Ops, query, target, max_dist: float, cell: float | None = N
     distances).  stats: a dict that receives the early-exit figures (tools/cloud_eval_bench.py)."""
     if not (max_dist > 0 and math.isfinite(max_dist)):
         raise ValueError(f"max_dist must be positive and finite, got {max_dist}")
-    query, target = _to_cloud(ops, query), _to_cloud(ops, target)
+    query, target = to_cloud(ops, query), to_cloud(ops, target)
     if cell is None:
         cell = min(float(max_dist), 2.0 * estimate_spacing(target, max_dist / FAR_RINGS)) if target.shape[0] else float(max_dist)
     cell = float(cell)
@@ -164,33 +94,6 @@ def _work_stats(wk, wk2, cell, cell2) -> dict:
         out.update({"far_cell": cell2, "far_queries": int(wk2.shape[0]), "far_share": wk2.shape[0] / n,
                     "far_mean_targets_tested": float(wk2[:, 1].double().mean())})
     return out
-
-
-# ------------------------------------------------------------------------------------------ thinning
-def voxel_downsample(xyz, voxel: float):
-    """keep, per occupied voxel of side `voxel` (lattice anchored at the coordinate origin), the point with the lowest input
-    index.  -> (points [K,3], index [K] int64 ascending) on the input's device.
-
-    This STANDS IN for the DTU scorer's thinning and is not the same algorithm: the MATLAB program walks the points in input
-    order and drops every point closer than `voxel` to one it has kept (greedy, serial, order-dependent; kept points are at
-    least `voxel` apart), whereas a voxel lattice keeps points that may be arbitrarily close across a voxel face and about as
-    many per area.  Scores computed after this thinning are therefore close to the official ones, not identical to them."""
-    t = torch.as_tensor(np.ascontiguousarray(xyz) if isinstance(xyz, np.ndarray) else xyz)
-    if not (voxel > 0 and math.isfinite(voxel)):
-        raise ValueError(f"voxel size must be positive and finite, got {voxel}")
-    if t.shape[0] == 0:
-        return t, torch.zeros(0, dtype=torch.int64, device=t.device)
-    c = torch.floor(t.double() / float(voxel)).long()
-    c = c - c.min(0).values
-    n = [int(v) + 1 for v in c.max(0).values.cpu()]
-    if sum(_bits(v) for v in n) > 62:
-        raise ValueError(f"a lattice of {n} voxels of side {voxel} exceeds the 62-bit key")
-    key = (c[:, 2] << (_bits(n[0]) + _bits(n[1]))) | (c[:, 1] << _bits(n[0])) | c[:, 0]
-    skey, order = torch.sort(key, stable=True)      # stable: the first entry of a run of equal keys is the lowest input index
-    first = torch.ones_like(skey, dtype=torch.bool)
-    first[1:] = skey[1:] != skey[:-1]
-    idx = torch.sort(order[first]).values
-    return t[idx], idx
 
 
 # ------------------------------------------------------------------------------------------ region of interest
@@ -244,10 +147,7 @@ def roi_plane_mask(points: torch.Tensor, roi: dict):
 # ------------------------------------------------------------------------------------------ metrics
 def fixed_scale(max_dist: float, n: int) -> float:
     """the largest power of two with max_dist * scale * max(n, 1) < 2^62: the u64 sum of rint(d * scale) cannot overflow"""
-    e = math.floor(math.log2(2.0 ** 62 / (float(max_dist) * max(1, n))))
-    while float(max_dist) * 2.0 ** e * max(1, n) >= 2.0 ** 62:
-        e -= 1
-    return 2.0 ** e
+    return pow2_scale_below(max_dist, n)
 
 
 def side_stats(ops: Ops, dist: torch.Tensor, valid, max_dist: float, thresholds, blocks: int = 0) -> dict:
@@ -275,7 +175,7 @@ def evaluate(ops: Ops, pred, gt, max_dist: float, thresholds, density: float | N
     out of completeness / recall, through the same masks as `roi`.  With any of the three the result also holds "transformation"
     (and "registration"); without them nothing changes."""
     thresholds = [float(t) for t in thresholds]
-    pred, gt = _to_cloud(ops, pred), _to_cloud(ops, gt)
+    pred, gt = to_cloud(ops, pred), to_cloud(ops, gt)
     n_pred_in = int(pred.shape[0])
     kept = None
     if density is not None:
@@ -284,14 +184,12 @@ def evaluate(ops: Ops, pred, gt, max_dist: float, thresholds, density: float | N
     if cell is None and density is not None:
         cell = 2.0 * float(density)
     reg = None
-    if transform is not None or crop is not None or register is not None:
-        from . import cloud_register as CR
-        if register is not None:
-            reg = CR.register(ops, pred, gt, init=transform, crop=crop, **register)
-            transform = np.array(reg["transformation"])
-        if transform is not None:
-            transform = np.array(transform, np.float64).reshape(4, 4)
-            pred = CR.apply_transform(pred, transform)
+    if register is not None:
+        reg = CR.register(ops, pred, gt, init=transform, crop=crop, **register)
+        transform = np.array(reg["transformation"])
+    if transform is not None:
+        transform = np.array(transform, np.float64).reshape(4, 4)
+        pred = CR.apply_transform(pred, transform)
     valid_p = roi_volume_mask(pred, roi) if roi is not None else None
     valid_g = roi_plane_mask(gt, roi) if roi is not None else None
     if crop is not None:
@@ -360,7 +258,6 @@ def main(argv=None):
     roi = load_roi(a.roi) if a.roi else (load_dtu_roi(a.dtu_obs_mask, a.dtu_plane) if a.dtu_obs_mask else None)
     extra = {}
     if a.transform or a.crop or a.register is not None:
-        from . import cloud_register as CR
         extra = {"transform": CR.load_transform(a.transform) if a.transform else None, "crop": CR.load_crop_json(a.crop) if a.crop else None,
                  "register": None if a.register is None else {"schedule": [(a.register_voxel, a.register, a.register_max_iter)], "with_scale": a.register_with_scale}}
     res = evaluate_files(Ops.for_device(a.device), a.pred, a.gt, a.max_dist, a.thresholds, density=a.density, roi=roi, error_ply=a.error_ply, **extra)

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from . import cloud_eval as CE
+from . import cloud_grid as G
 from . import formats as IO
 from .ops import Ops
 
@@ -107,38 +107,22 @@ def apply_transform(points: torch.Tensor, transform) -> torch.Tensor:
 # ------------------------------------------------------------------------------------------ ICP
 def moment_scales(n: int, bound: float, max_corr: float):
     """the largest powers of two the entry point accepts: n bound s1 < 2^62 and n max(3 bound^2, (1.001 max_corr)^2) s2 < 2^62"""
-    out = []
-    for big in (float(bound), max(3.0 * bound * bound, (1.001 * float(np.float32(max_corr))) ** 2)):
-        e = math.floor(math.log2(2.0 ** 62 / (big * max(1, n))))
-        while big * 2.0 ** e * max(1, n) >= 2.0 ** 62:
-            e -= 1
-        out.append(2.0 ** e)
-    return tuple(out)
-
-
-def _sort_by_grid(points: torch.Tensor, grid: dict):
-    """the order of `points` by the grid's key (grid_nn's idiom): neighbouring lanes then walk and gather the same cells"""
-    if points.shape[0] == 0 or grid["keys"].numel() == 0:
-        return None
-    dims = grid["dims"]
-    hi = torch.tensor([n - 1 for n in dims], device=points.device)
-    c = CE._cells(torch.nan_to_num(points, nan=0.0, posinf=3e38, neginf=-3e38), grid["origin"], grid["cell"])
-    return torch.sort(CE._key(torch.minimum(c.clamp_min_(0), hi), dims)).indices
+    return G.pow2_scale_below(bound, n), G.pow2_scale_below(max(3.0 * bound * bound, (1.001 * float(np.float32(max_corr))) ** 2), n)
 
 
 def icp(ops: Ops, source, target, init=None, max_corr: float = None, max_iter: int = 30, rel_fitness: float = 1e-6, rel_rmse: float = 1e-6,
-        with_scale: bool = False, valid=None, cell: float | None = None, grid: dict | None = None, timers: dict | None = None) -> dict:
+        with_scale: bool = False, valid=None, cell: float | None = None, grid: dict | None = None) -> dict:
     """point-to-point ICP of `source` [N,3] onto `target` [M,3] from the 4x4 `init` (identity by default).
 
     -> {transformation (4x4 float64 nested list: source -> target frame), fitness (pairs / source points), inlier_rmse
     (sqrt(sum d^2 / pairs)), pairs, iterations (updates applied), converged, history: [{fitness, inlier_rmse, pairs}] (entry 0 = the
     initial transform)}.  A pair is a source point whose nearest target lies within max_corr.  valid: optional uint8 [N], points with
-    0 take no part (and do not count as source points).  The target grid is built once (or passed in: cloud_eval.build_grid), the
+    0 take no part (and do not count as source points).  The target grid is built once (or passed in: cloud_grid.build_grid), the
     source is sorted by the grid key of its initially transformed position once.  Raises ValueError when an update is undetermined
     (fewer than 3 pairs, collinear pairs)."""
     if max_corr is None or not (max_corr > 0 and math.isfinite(max_corr)):
         raise ValueError(f"max_corr must be positive and finite, got {max_corr}")
-    src, tgt = CE._to_cloud(ops, source), CE._to_cloud(ops, target)
+    src, tgt = G.to_cloud(ops, source), G.to_cloud(ops, target)
     if src.shape[0] == 0 or tgt.shape[0] == 0:
         raise ValueError("icp: both clouds must hold points")
     T = np.eye(4) if init is None else np.array(init, np.float64).reshape(4, 4)
@@ -146,9 +130,9 @@ def icp(ops: Ops, source, target, init=None, max_corr: float = None, max_iter: i
         valid = torch.as_tensor(valid).to(device=ops.device, dtype=torch.uint8).contiguous()
     if grid is None:
         if cell is None:
-            cell = min(float(max_corr), max(2.0 * CE.estimate_spacing(tgt, max_corr / CE.FAR_RINGS), float(max_corr) / CE.FAR_RINGS))
-        grid = CE.build_grid(tgt, float(cell))
-    order = _sort_by_grid(apply_transform(src, T), grid)
+            cell = min(float(max_corr), max(2.0 * G.estimate_spacing(tgt, max_corr / G.FAR_RINGS), float(max_corr) / G.FAR_RINGS))
+        grid = G.build_grid(tgt, float(cell))
+    order = G.order_by_grid(apply_transform(src, T), grid)
     if order is not None:
         src = src[order].contiguous()
         valid = None if valid is None else valid[order].contiguous()
@@ -161,18 +145,8 @@ def icp(ops: Ops, source, target, init=None, max_corr: float = None, max_iter: i
     scales = moment_scales(int(src.shape[0]), bound, max_corr)
 
     def evaluate(Tm):
-        def timed(name, fn):
-            if timers is None:
-                return fn()
-            st, en = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            st.record()
-            r = fn()
-            en.record()
-            timers.setdefault(name, []).append((st, en))
-            return r
-        index = timed("search", lambda: ops.cloud_nn_index(src, gt_sorted, grid["keys"], grid["start"], grid["origin"], grid["cell"], grid["dims"],
-                                                           max_corr, transform=Tm, dist=False)[1])
-        mom = timed("moments", lambda: ops.cloud_pair_moments(src, Tm, gt_sorted, index, valid, max_corr, centre, centre, bound, scales[0], scales[1]))
+        index = ops.cloud_nn_index(src, gt_sorted, grid["keys"], grid["start"], grid["origin"], grid["cell"], grid["dims"], max_corr, transform=Tm, dist=False)[1]
+        mom = ops.cloud_pair_moments(src, Tm, gt_sorted, index, valid, max_corr, centre, centre, bound, scales[0], scales[1])
         m = [int(v) for v in mom.cpu()]
         if m[19]:
             raise RuntimeError(f"icp: {m[19]} pairs left the fixed-point bound {bound}")
@@ -219,7 +193,7 @@ def load_crop_json(path: str) -> dict:
 
 def crop_mask(ops: Ops, points, volume: dict, transform=None) -> torch.Tensor:
     """uint8 [N]: 1 where the point (moved by the 4x4 `transform` first, if given) lies inside the volume (dmvs_cloud_crop_prism_f32)"""
-    pts = CE._to_cloud(ops, points)
+    pts = G.to_cloud(ops, points)
     poly = torch.from_numpy(volume["polygon"]).to(ops.device).contiguous()
     return ops.cloud_crop_prism(pts, poly, volume["axis"], volume["axis_min"], volume["axis_max"], transform=transform)
 
@@ -262,7 +236,7 @@ def tanks_schedule(dtau: float):
 def register(ops: Ops, pred, gt, init=None, schedule=None, crop: dict | None = None, with_scale: bool = False, rel_fitness: float = 1e-6,
              rel_rmse: float = 1e-6) -> dict:
     """coarse-to-fine ICP: `schedule` is a list of stages (voxel, max_corr, max_iter); each stage thins both clouds with
-    cloud_eval.voxel_downsample(voxel) (voxel None: not at all), keeps only the prediction points that its starting transform puts
+    cloud_grid.voxel_downsample(voxel) (voxel None: not at all), keeps only the prediction points that its starting transform puts
     inside `crop` (if given) and runs `icp` from the previous stage's result.  -> the last stage's dict plus "stages".
 
     tanks_schedule(dtau) fills in the Tanks&Temples toolbox's stages (voxel dtau / corr 80 dtau, voxel dtau / 2 / corr 20 dtau, no
@@ -272,12 +246,12 @@ def register(ops: Ops, pred, gt, init=None, schedule=None, crop: dict | None = N
     (3) the toolbox's last stage thins by taking every k-th point down to a maximum size, this one uses all points."""
     if not schedule:
         raise ValueError("register: an empty schedule")
-    pred, gt = CE._to_cloud(ops, pred), CE._to_cloud(ops, gt)
+    pred, gt = G.to_cloud(ops, pred), G.to_cloud(ops, gt)
     T = np.eye(4) if init is None else np.array(init, np.float64).reshape(4, 4)
     stages, res = [], None
     for voxel, max_corr, max_iter in schedule:
-        s = pred if voxel is None else CE.voxel_downsample(pred, voxel)[0].contiguous()
-        t = gt if voxel is None else CE.voxel_downsample(gt, voxel)[0].contiguous()
+        s = pred if voxel is None else G.voxel_downsample(pred, voxel)[0].contiguous()
+        t = gt if voxel is None else G.voxel_downsample(gt, voxel)[0].contiguous()
         if crop is not None:
             s = s[crop_mask(ops, s, crop, transform=T).bool()].contiguous()
         res = icp(ops, s, t, init=T, max_corr=max_corr, max_iter=int(max_iter), rel_fitness=rel_fitness, rel_rmse=rel_rmse, with_scale=with_scale)
@@ -317,7 +291,7 @@ def main(argv=None):
                    crop=load_crop_json(a.crop) if a.crop else None, with_scale=a.with_scale)
     save_transform(a.out_transform, res["transformation"])
     if a.out_ply:
-        moved = apply_transform(CE._to_cloud(ops, pred), res["transformation"]).cpu().numpy()
+        moved = apply_transform(G.to_cloud(ops, pred), res["transformation"]).cpu().numpy()
         IO.write_ply(a.out_ply, moved, colour if colour is not None else np.zeros((len(moved), 3), np.uint8))
     print(json.dumps(res), flush=True)
     return res

@@ -33,10 +33,8 @@ struct CloudThresholds { float t[CLOUD_MAX_T]; };
 __global__ void __launch_bounds__(DMVS_BLOCK)
 cloud_stats_kernel(const float* __restrict__ dist, const uint8_t* __restrict__ valid, long N, float max_dist, CloudThresholds thr, int T, double scale,
                    unsigned long long* __restrict__ out) {
-    __shared__ unsigned long long part[DMVS_BLOCK / 64][CLOUD_NCOUNT];
-    unsigned long long n_valid = 0, n_in = 0, sum = 0, below[CLOUD_MAX_T];
-#pragma unroll
-    for (int t = 0; t < CLOUD_MAX_T; ++t) below[t] = 0;
+    CloudSums<CLOUD_NCOUNT> acc = {};
+    unsigned long long &n_valid = acc.v[0], &n_in = acc.v[1], &sum = acc.v[2], *const below = acc.v + 3;
     const long stride = (long)gridDim.x * DMVS_BLOCK;
     for (long i = (long)blockIdx.x * DMVS_BLOCK + threadIdx.x; i < N; i += stride) {
         if (valid && !valid[i]) continue;
@@ -49,25 +47,7 @@ cloud_stats_kernel(const float* __restrict__ dist, const uint8_t* __restrict__ v
 #pragma unroll
         for (int t = 0; t < CLOUD_MAX_T; ++t) below[t] += d < thr.t[t] ? 1ull : 0ull;      // unused slots hold -inf
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        n_valid += __shfl_down(n_valid, off);
-        n_in += __shfl_down(n_in, off);
-        sum += __shfl_down(sum, off);
-#pragma unroll
-        for (int t = 0; t < CLOUD_MAX_T; ++t) below[t] += __shfl_down(below[t], off);
-    }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        part[wave][0] = n_valid, part[wave][1] = n_in, part[wave][2] = sum;
-#pragma unroll
-        for (int t = 0; t < CLOUD_MAX_T; ++t) part[wave][3 + t] = below[t];
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < 3 + T) {
-        unsigned long long v = 0;
-        for (int w = 0; w < DMVS_BLOCK / 64; ++w) v += part[w][threadIdx.x];
-        if (v) atomicAdd(out + threadIdx.x, v);
-    }
+    cloud_block_sum(acc, 3 + T, out);
 }
 
 }  // namespace
@@ -75,25 +55,13 @@ cloud_stats_kernel(const float* __restrict__ dist, const uint8_t* __restrict__ v
 extern "C" int dmvs_cloud_nn_dist_f32(const float* query, int64_t Q, const float* target, int64_t M, const int64_t* cell_keys,
                                       const int64_t* cell_start, int64_t C, const double* origin, double h, const int32_t* dims,
                                       float max_dist, float* dist, int32_t* work, void* stream) {
-    if (Q > 0 && (!query || !dist)) return DMVS_EINVAL;
-    CloudGrid g;
-    const int rc = cloud_grid_args(Q, M, target, cell_keys, cell_start, C, origin, h, dims, max_dist, g);
-    if (rc != 0) return rc;
-    if (Q == 0) return 0;
-    dim3 grid(dmvs_ceil_div(Q, DMVS_BLOCK)), block(DMVS_BLOCK);
-    CloudTransform T;
-    cloud_transform_arg(nullptr, T);
-    hipLaunchKernelGGL(cloud_nn_kernel<false>, grid, block, 0, (hipStream_t)stream, query, (long)Q, target, g, max_dist, T, dist, (int32_t*)nullptr, work);
-    return dmvs_launch_status();
+    return cloud_nn_launch<false>(query, Q, target, M, cell_keys, cell_start, C, origin, h, dims, max_dist, nullptr, dist, nullptr, work, stream);
 }
 
 extern "C" int dmvs_cloud_stats_f32(const float* dist, const uint8_t* valid, int64_t N, float max_dist, const float* thresholds, int32_t T,
                                     double scale, int32_t blocks, uint64_t* out, void* stream) {
     if (N < 0 || T < 0 || T > CLOUD_MAX_T || !out || blocks < 0 || (N > 0 && !dist) || (T > 0 && !thresholds)) return DMVS_EINVAL;
-    if (!(max_dist > 0.0f) || !isfinite(max_dist) || !(scale > 0.0) || !isfinite(scale)) return DMVS_EINVAL;
-    int e = 0;
-    if (frexp(scale, &e) != 0.5) return DMVS_EINVAL;                                       // not a power of two
-    if (!((double)max_dist * scale * (double)(N > 0 ? N : 1) < 4611686018427387904.0)) return DMVS_EINVAL;      // 2^62: the sum cannot overflow
+    if (!(max_dist > 0.0f) || !isfinite(max_dist) || !cloud_pow2(scale) || !cloud_sum_fits(N, (double)max_dist, scale)) return DMVS_EINVAL;
     CloudThresholds thr;
     for (int t = 0; t < CLOUD_MAX_T; ++t) {
         thr.t[t] = t < T ? thresholds[t] : -INFINITY;
@@ -104,10 +72,7 @@ extern "C" int dmvs_cloud_stats_f32(const float* dist, const uint8_t* valid, int
     const hipError_t err = hipMemsetAsync(acc, 0, (size_t)(3 + T) * sizeof(unsigned long long), s);
     if (err != hipSuccess) return (int)err;
     if (N == 0) return 0;
-    long nb = (N + DMVS_BLOCK - 1) / DMVS_BLOCK;
-    const long cap = blocks > 0 ? blocks : 4096;          // a grid-stride loop: a few thousand workgroups keep the atomics few
-    if (nb > cap) nb = cap;
-    dim3 grid((unsigned)nb), block(DMVS_BLOCK);
+    dim3 grid(cloud_sum_blocks(N, blocks)), block(DMVS_BLOCK);
     hipLaunchKernelGGL(cloud_stats_kernel, grid, block, 0, s, dist, valid, (long)N, max_dist, thr, (int)T, scale, acc);
     return dmvs_launch_status();
 }

@@ -40,10 +40,8 @@ cloud_pair_moments_kernel(const float* __restrict__ source, long N, CloudTransfo
                           const int32_t* __restrict__ index, const uint8_t* __restrict__ valid, CloudMomentArgs a,
                           unsigned long long* __restrict__ out) {
 #pragma clang fp contract(off)
-    __shared__ unsigned long long part[DMVS_BLOCK / 64][CLOUD_NMOM];
-    unsigned long long acc[CLOUD_NMOM];
-#pragma unroll
-    for (int k = 0; k < CLOUD_NMOM; ++k) acc[k] = 0;
+    CloudSums<CLOUD_NMOM> sums = {};
+    unsigned long long* const acc = sums.v;
     const long stride = (long)gridDim.x * DMVS_BLOCK;
     for (long i = (long)blockIdx.x * DMVS_BLOCK + threadIdx.x; i < N; i += stride) {
         const long j = index[i];
@@ -77,21 +75,7 @@ cloud_pair_moments_kernel(const float* __restrict__ source, long N, CloudTransfo
         acc[17] += cloud_fix(((t0 * t0 + t1 * t1) + t2 * t2) * a.s2);
         acc[18] += cloud_fix(((r0 * r0 + r1 * r1) + r2 * r2) * a.s2);
     }
-    for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-        for (int k = 0; k < CLOUD_NMOM; ++k) acc[k] += __shfl_down(acc[k], off);
-    }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < CLOUD_NMOM; ++k) part[wave][k] = acc[k];
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < CLOUD_NMOM) {
-        unsigned long long v = 0;
-        for (int w = 0; w < DMVS_BLOCK / 64; ++w) v += part[w][threadIdx.x];
-        if (v) atomicAdd(out + threadIdx.x, v);
-    }
+    cloud_block_sum(sums, CLOUD_NMOM, out);
 }
 
 struct CloudPrism {
@@ -124,27 +108,12 @@ cloud_crop_prism_kernel(const float* __restrict__ points, long N, CloudTransform
     inside[i] = (uint8_t)((in && w >= P.lo && w <= P.hi) ? 1 : 0);
 }
 
-bool cloud_pow2(double s) {
-    int e = 0;
-    return s > 0.0 && isfinite(s) && frexp(s, &e) == 0.5;
-}
-
 }  // namespace
 
 extern "C" int dmvs_cloud_nn_index_f32(const float* query, int64_t Q, const float* target, int64_t M, const int64_t* cell_keys,
                                        const int64_t* cell_start, int64_t C, const double* origin, double h, const int32_t* dims,
                                        float max_dist, const double* transform, float* dist, int32_t* index, int32_t* work, void* stream) {
-    if (Q > 0 && (!query || !index)) return DMVS_EINVAL;
-    if (M > 2147483647L) return DMVS_EINVAL;                // the index is 32 bits
-    CloudGrid g;
-    const int rc = cloud_grid_args(Q, M, target, cell_keys, cell_start, C, origin, h, dims, max_dist, g);
-    if (rc != 0) return rc;
-    CloudTransform T;
-    if (cloud_transform_arg(transform, T) != 0) return DMVS_EINVAL;
-    if (Q == 0) return 0;
-    dim3 grid(dmvs_ceil_div(Q, DMVS_BLOCK)), block(DMVS_BLOCK);
-    hipLaunchKernelGGL(cloud_nn_kernel<true>, grid, block, 0, (hipStream_t)stream, query, (long)Q, target, g, max_dist, T, dist, index, work);
-    return dmvs_launch_status();
+    return cloud_nn_launch<true>(query, Q, target, M, cell_keys, cell_start, C, origin, h, dims, max_dist, transform, dist, index, work, stream);
 }
 
 extern "C" int dmvs_cloud_pair_moments_f64(const float* source, int64_t N, const double* transform, const float* target, int64_t M,
@@ -162,9 +131,8 @@ extern "C" int dmvs_cloud_pair_moments_f64(const float* source, int64_t N, const
         if (!isfinite(a.cp[k]) || !isfinite(a.cq[k])) return DMVS_EINVAL;
     }
     // no sum can reach 2^62: |p_k|, |t_k| <= bound, so |p|^2, |t|^2, |p_a t_b| <= 3 bound^2, and a counted pair is at most max_corr apart
-    const double n = (double)(N > 0 ? N : 1), mc = (double)max_corr * 1.001;
-    const double quad = fmax(3.0 * bound * bound, mc * mc);
-    if (!(n * bound * scale_linear < 4611686018427387904.0) || !(n * quad * scale_quadratic < 4611686018427387904.0)) return DMVS_EINVAL;
+    const double mc = (double)max_corr * 1.001;
+    if (!cloud_sum_fits(N, bound, scale_linear) || !cloud_sum_fits(N, fmax(3.0 * bound * bound, mc * mc), scale_quadratic)) return DMVS_EINVAL;
     CloudTransform T;
     if (cloud_transform_arg(transform, T) != 0) return DMVS_EINVAL;
     a.bound = bound, a.s1 = scale_linear, a.s2 = scale_quadratic, a.max_corr = max_corr;
@@ -173,10 +141,7 @@ extern "C" int dmvs_cloud_pair_moments_f64(const float* source, int64_t N, const
     const hipError_t err = hipMemsetAsync(acc, 0, (size_t)CLOUD_NMOM * sizeof(unsigned long long), s);
     if (err != hipSuccess) return (int)err;
     if (N == 0) return 0;
-    long nb = (N + DMVS_BLOCK - 1) / DMVS_BLOCK;
-    const long cap = blocks > 0 ? blocks : 4096;          // a grid-stride loop: a few thousand workgroups keep the atomics few
-    if (nb > cap) nb = cap;
-    dim3 grid((unsigned)nb), block(DMVS_BLOCK);
+    dim3 grid(cloud_sum_blocks(N, blocks)), block(DMVS_BLOCK);
     hipLaunchKernelGGL(cloud_pair_moments_kernel, grid, block, 0, s, source, (long)N, T, target, (long)M, index, valid, a, acc);
     return dmvs_launch_status();
 }

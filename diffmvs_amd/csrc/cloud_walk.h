@@ -1,7 +1,8 @@
 // The grid walk of the point-cloud kernels, shared by dmvs_cloud_nn_dist_f32 (cloud_eval.hip) and dmvs_cloud_nn_index_f32
 // (cloud_register.hip); the walk itself is described at the top of cloud_eval.hip.  INDEX = true also tracks WHICH target is the
 // nearest (one more register and a select per target tested); with INDEX = false that member is never read and the walk compiles
-// to what it was before the index search existed.
+// to what it was before the index search existed.  Also here: what the fixed-point reductions of both files share (cloud_block_sum
+// and the host-side shaping of its launches).
 #pragma once
 #include <math.h>
 #include "dmvs_common.h"
@@ -181,6 +182,46 @@ cloud_nn_kernel(const float* __restrict__ query, long Q, const float* __restrict
     }
 }
 
+// The project's fixed-point reduction (dmvs_cloud_stats_f32, dmvs_cloud_pair_moments_f64): every lane of a DMVS_BLOCK workgroup brings N
+// u64 partial sums; waves reduce with shuffles, the workgroup through LDS, then ONE integer atomicAdd per counter per workgroup into
+// out[0 .. live).  Integer sums are associative, so the totals are bitwise independent of launch order and grid shape.
+template <int N> struct CloudSums { unsigned long long v[N]; };
+
+template <int N>
+__device__ __forceinline__ void cloud_block_sum(CloudSums<N> acc, int live, unsigned long long* out) {
+    __shared__ unsigned long long part[DMVS_BLOCK / 64][N];
+    for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) acc.v[k] += __shfl_down(acc.v[k], off);
+    }
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) part[wave][k] = acc.v[k];
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < live) {
+        unsigned long long v = 0;
+        for (int w = 0; w < DMVS_BLOCK / 64; ++w) v += part[w][threadIdx.x];
+        if (v) atomicAdd(out + threadIdx.x, v);
+    }
+}
+
+// host side of such a launch: the scale is a positive finite power of two ...
+inline bool cloud_pow2(double s) {
+    int e = 0;
+    return s > 0.0 && isfinite(s) && frexp(s, &e) == 0.5;
+}
+
+// ... no sum of N terms of at most `big` can reach 2^62 ...
+inline bool cloud_sum_fits(int64_t N, double big, double scale) { return (double)(N > 0 ? N : 1) * big * scale < 4611686018427387904.0; }
+
+// ... and the kernel is a grid-stride loop: a few thousand workgroups (or `blocks`) keep the atomics few
+inline unsigned cloud_sum_blocks(int64_t N, int32_t blocks) {
+    const long nb = (N + DMVS_BLOCK - 1) / DMVS_BLOCK, cap = blocks > 0 ? blocks : 4096;
+    return (unsigned)(nb < cap ? nb : cap);
+}
+
 inline int cloud_bits(long n) {
     int b = 0;
     while ((1L << b) < n) ++b;
@@ -214,6 +255,24 @@ inline int cloud_transform_arg(const double* transform, CloudTransform& T) {
         if (!isfinite(T.m[k])) return DMVS_EINVAL;
     }
     return 0;
+}
+
+// the two searches: dist is required without INDEX (and may be NULL with it), index and a 32-bit M with INDEX only
+template <bool INDEX>
+inline int cloud_nn_launch(const float* query, int64_t Q, const float* target, int64_t M, const int64_t* cell_keys, const int64_t* cell_start,
+                           int64_t C, const double* origin, double h, const int32_t* dims, float max_dist, const double* transform, float* dist,
+                           int32_t* index, int32_t* work, void* stream) {
+    if (Q > 0 && (!query || (INDEX ? !index : !dist))) return DMVS_EINVAL;
+    if (INDEX && M > 2147483647L) return DMVS_EINVAL;      // the index is 32 bits
+    CloudGrid g;
+    const int rc = cloud_grid_args(Q, M, target, cell_keys, cell_start, C, origin, h, dims, max_dist, g);
+    if (rc != 0) return rc;
+    CloudTransform T;
+    if (cloud_transform_arg(transform, T) != 0) return DMVS_EINVAL;
+    if (Q == 0) return 0;
+    dim3 grid(dmvs_ceil_div(Q, DMVS_BLOCK)), block(DMVS_BLOCK);
+    hipLaunchKernelGGL(cloud_nn_kernel<INDEX>, grid, block, 0, (hipStream_t)stream, query, (long)Q, target, g, max_dist, T, dist, index, work);
+    return dmvs_launch_status();
 }
 
 }  // namespace

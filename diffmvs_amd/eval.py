@@ -183,10 +183,9 @@ def main(argv=None):
             res.setdefault("fused_points", {})[scene] = n
             res.setdefault("ply", {})[scene] = kw["plyfilename"]
             if a.gt_ply:
-                from . import cloud_eval
+                from . import cloud_eval, cloud_register
                 extra = {}
                 if a.gt_transform or a.gt_crop:
-                    from . import cloud_register
                     extra = {"transform": cloud_register.load_transform(a.gt_transform.replace("{scene}", scene)) if a.gt_transform else None,
                              "crop": cloud_register.load_crop_json(a.gt_crop.replace("{scene}", scene)) if a.gt_crop else None}
                 from .ops import Ops

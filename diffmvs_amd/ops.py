@@ -279,6 +279,11 @@ class Ops:
                 raise _lib.DmvsError(f"expected contiguous fp32 tensor on {self.device}, got {t.dtype} "
                                      f"contiguous={t.is_contiguous()} on {t.device}")
 
+    def _chk_typed(self, what, *pairs):
+        for t, dt in pairs:
+            if t is not None and (t.dtype != dt or not t.is_contiguous() or t.device != self.device):
+                raise _lib.DmvsError(f"{what}: expected a contiguous {dt} tensor on {self.device}, got {t.dtype} on {t.device}")
+
     # ------------------------------------------------------------------ conv2d
     def conv2d(self, pc: PackedConv, x0, x1=None, *, mul0=None, in_mode=IN_PLAIN, act=ACT_NONE, residual=None,
                res_mode=IN_PLAIN, res_after_act=False, post_scale=1.0, gru_z=None, gru_h=None, out=None,
@@ -751,9 +756,7 @@ class Ops:
     def view_scores(self, xyz, offsets, images, mult, centres, theta0=5.0, sigma1=1.0, sigma2=10.0):
         """dmvs_view_select_scores_f64: the [N,N] fp64 pair scores of colmap_input.py:374-390 from a point -> image CSR (include/dmvs.h).
         xyz [P,3] / centres [N,3] fp64, offsets [P+1] int64, images / mult [E] int32, all on this binding's device."""
-        for t, dt in ((xyz, torch.float64), (centres, torch.float64), (offsets, torch.int64), (images, torch.int32), (mult, torch.int32)):
-            if t.dtype != dt or not t.is_contiguous() or t.device != self.device:
-                raise _lib.DmvsError(f"view_scores: expected a contiguous {dt} tensor on {self.device}, got {t.dtype} on {t.device}")
+        self._chk_typed("view_scores", (xyz, torch.float64), (centres, torch.float64), (offsets, torch.int64), (images, torch.int32), (mult, torch.int32))
         N, P = int(centres.shape[0]), int(xyz.shape[0])
         if not 1 <= N <= _lib.VIEW_SELECT_MAX_IMAGES:
             raise _lib.DmvsError(f"view_scores: {N} images; the score matrix supports 1..{_lib.VIEW_SELECT_MAX_IMAGES}")
@@ -774,27 +777,30 @@ class Ops:
         return out
 
     # ------------------------------------------------------------------ point-cloud scoring (diffmvs_amd/cloud_eval.py)
-    def _chk_typed(self, what, *pairs):
-        for t, dt in pairs:
-            if t is not None and (t.dtype != dt or not t.is_contiguous() or t.device != self.device):
-                raise _lib.DmvsError(f"{what}: expected a contiguous {dt} tensor on {self.device}, got {t.dtype} on {t.device}")
+    def _cloud_nn(self, what, query, target, cell_keys, cell_start, origin, h, dims, max_dist, transform, want_dist, want_index, work):
+        """the checks and the call both grid searches share -> (dist or None, index or None, work or None)"""
+        self._chk_typed(what, (query, torch.float32), (target, torch.float32), (cell_keys, torch.int64), (cell_start, torch.int64))
+        Q, M, Cn = int(query.shape[0]), int(target.shape[0]), int(cell_keys.numel())
+        if query.dim() != 2 or query.shape[1] != 3 or target.dim() != 2 or target.shape[1] != 3:
+            raise _lib.DmvsError(f"{what}: query and target must be [N,3]")
+        if cell_start.numel() != Cn + 1 or Cn > M or (M > 0 and Cn < 1):
+            raise _lib.DmvsError(f"{what}: cell_start must have one entry more than cell_keys, and every target a cell")
+        dist = self.empty(Q) if want_dist else None
+        index = torch.empty(Q, dtype=torch.int32, device=self.device) if want_index else None
+        wk = torch.empty(Q, 2, dtype=torch.int32, device=self.device) if work else None
+        grid = (_ptr(query), Q, _ptr(target), M, _ptr(cell_keys), _ptr(cell_start), Cn, (C.c_double * 3)(*[float(v) for v in origin]), float(h),
+                (C.c_int32 * 3)(*[int(v) for v in dims]), float(max_dist))
+        if want_index:
+            self._call("dmvs_cloud_nn_index_f32", *grid, self._transform_arg(transform), _ptr(dist), _ptr(index), _ptr(wk), self.stream())
+        else:
+            self._call("dmvs_cloud_nn_dist_f32", *grid, _ptr(dist), _ptr(wk), self.stream())
+        return dist, index, wk
 
     def cloud_nn_dist(self, query, target, cell_keys, cell_start, origin, h, dims, max_dist, work=False):
         """dmvs_cloud_nn_dist_f32: min(|q - nearest target|, max_dist) per query (include/dmvs.h).  query [Q,3] / target [M,3] fp32 with the
         targets sorted by cell key, cell_keys [C] / cell_start [C+1] int64, origin 3 floats, dims 3 ints.
         -> dist [Q] fp32, or (dist, work [Q,2] int32: rings walked, targets tested) with work=True."""
-        self._chk_typed("cloud_nn_dist", (query, torch.float32), (target, torch.float32), (cell_keys, torch.int64), (cell_start, torch.int64))
-        Q, M, Cn = int(query.shape[0]), int(target.shape[0]), int(cell_keys.numel())
-        if query.dim() != 2 or query.shape[1] != 3 or target.dim() != 2 or target.shape[1] != 3:
-            raise _lib.DmvsError("cloud_nn_dist: query and target must be [N,3]")
-        if cell_start.numel() != Cn + 1 or Cn > M or (M > 0 and Cn < 1):
-            raise _lib.DmvsError("cloud_nn_dist: cell_start must have one entry more than cell_keys, and every target a cell")
-        dist = self.empty(Q)
-        wk = torch.empty(Q, 2, dtype=torch.int32, device=self.device) if work else None
-        o = (C.c_double * 3)(*[float(v) for v in origin])
-        d = (C.c_int32 * 3)(*[int(v) for v in dims])
-        self._call("dmvs_cloud_nn_dist_f32", _ptr(query), Q, _ptr(target), M, _ptr(cell_keys), _ptr(cell_start), Cn, o, float(h), d,
-                   float(max_dist), _ptr(dist), _ptr(wk), self.stream())
+        dist, _, wk = self._cloud_nn("cloud_nn_dist", query, target, cell_keys, cell_start, origin, h, dims, max_dist, None, True, False, work)
         return (dist, wk) if work else dist
 
     def cloud_stats(self, dist, valid, max_dist, thresholds, scale, blocks=0):
@@ -827,19 +833,7 @@ class Ops:
     def cloud_nn_index(self, query, target, cell_keys, cell_start, origin, h, dims, max_dist, transform=None, dist=True, work=False):
         """dmvs_cloud_nn_index_f32: cloud_nn_dist on the query moved by `transform`, plus the position of the nearest target in the
         sorted target array (-1 where nothing is closer than max_dist).  -> (dist [Q] fp32 or None, index [Q] int32[, work [Q,2]])."""
-        self._chk_typed("cloud_nn_index", (query, torch.float32), (target, torch.float32), (cell_keys, torch.int64), (cell_start, torch.int64))
-        Q, M, Cn = int(query.shape[0]), int(target.shape[0]), int(cell_keys.numel())
-        if query.dim() != 2 or query.shape[1] != 3 or target.dim() != 2 or target.shape[1] != 3:
-            raise _lib.DmvsError("cloud_nn_index: query and target must be [N,3]")
-        if cell_start.numel() != Cn + 1 or Cn > M or (M > 0 and Cn < 1):
-            raise _lib.DmvsError("cloud_nn_index: cell_start must have one entry more than cell_keys, and every target a cell")
-        d = self.empty(Q) if dist else None
-        index = torch.empty(Q, dtype=torch.int32, device=self.device)
-        wk = torch.empty(Q, 2, dtype=torch.int32, device=self.device) if work else None
-        o = (C.c_double * 3)(*[float(v) for v in origin])
-        dm = (C.c_int32 * 3)(*[int(v) for v in dims])
-        self._call("dmvs_cloud_nn_index_f32", _ptr(query), Q, _ptr(target), M, _ptr(cell_keys), _ptr(cell_start), Cn, o, float(h), dm,
-                   float(max_dist), self._transform_arg(transform), _ptr(d), _ptr(index), _ptr(wk), self.stream())
+        d, index, wk = self._cloud_nn("cloud_nn_index", query, target, cell_keys, cell_start, origin, h, dims, max_dist, transform, dist, True, work)
         return (d, index, wk) if work else (d, index)
 
     def cloud_pair_moments(self, source, transform, target, index, valid, max_corr, center_p, center_q, bound, scale_linear, scale_quadratic,

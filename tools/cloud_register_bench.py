@@ -80,16 +80,20 @@ def main():
     kw = dict(max_corr=a.max_corr, max_iter=a.iters, rel_fitness=0.0, rel_rmse=0.0)
     res = CR.icp(ops, src, tgt, **kw)          # warm-up
     torch.cuda.synchronize()
+    names = {"search": "dmvs_cloud_nn_index_f32", "moments": "dmvs_cloud_pair_moments_f64"}
     walls, splits = [], []
-    for _ in range(a.reps):
-        timers = {}
-        st, en = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        st.record()
-        res = CR.icp(ops, src, tgt, timers=timers, **kw)
-        en.record()
-        torch.cuda.synchronize()
-        walls.append(st.elapsed_time(en))
-        splits.append({k: [s.elapsed_time(e) for s, e in v] for k, v in timers.items()})
+    try:
+        for _ in range(a.reps):
+            ops.timers = {n: [] for n in names.values()}
+            st, en = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            st.record()
+            res = CR.icp(ops, src, tgt, **kw)
+            en.record()
+            torch.cuda.synchronize()
+            walls.append(st.elapsed_time(en))
+            splits.append({k: [s.elapsed_time(e) for s, e in ops.timers[n]] for k, n in names.items()})
+    finally:
+        ops.timers = None
     i = int(np.argmin(walls))
     search, moments = splits[i]["search"], splits[i]["moments"]
     launches = len(search)
