@@ -613,64 +613,234 @@ def test_getcost_extreme_geometry(ops, golden):
             assert float((got - w).abs().mean()) <= 2e-3 * max(1.0, float(w.abs().mean())), (ci, d)
 
 
-def test_misc_kernels(ops):
-    B, S, G, D, H, W = 2, 3, 4, 6, 5, 7
+# ------------------------------------------------------------------------------------------ streaming kernels (misc.hip)
+# One test per kernel, against fp64 formulas of the same fp32 inputs written out here.  Planes of 19 x 23 = 437 (no multiple of 4) and
+# 20 x 24 = 480 pixels with B = 3: every launch has several 256-lane workgroups, and workgroups straddle plane and batch boundaries.
+_SENTINEL = -777.25
+
+
+def err64(what, got, want, tol):
+    """close() against an fp64 reference; prints the figure first (pytest -rP shows it: the measured maxima of a GPU run)"""
+    got = got.detach().cpu()
+    assert got.dtype == torch.float32 and want.dtype == torch.float64, (got.dtype, want.dtype)
+    assert got.shape == want.shape, (got.shape, want.shape)
+    err = float((got.double() - want).abs().max())
+    print(f"{what}: max abs err vs fp64 {err:.3e} (scale {max(1.0, float(want.abs().max())):.3e}, tol {tol:g})")
+    close(got, want, tol)
+    return err
+
+
+def _disp_range(B):
+    """inverse-depth range [disp_min, disp_max] per batch item, different for every item -> two [B] fp32 tensors"""
+    lo = torch.tensor([1 / 935.0, 1 / 800.0, 1 / 1100.0, 1 / 640.0])[:B].contiguous()
+    hi = torch.tensor([1 / 425.0, 1 / 500.0, 1 / 380.0, 1 / 300.0])[:B].contiguous()
+    return lo, hi
+
+
+def _disp_to_depth64(nd, lo, hi):
+    """nd [B, ...] normalised inverse depth -> metric depth, fp64 (models/module.py:220-227)"""
+    lo, hi = [t.double().view(-1, *([1] * (nd.dim() - 1))) for t in (lo, hi)]
+    return 1.0 / (lo + (hi - lo) * nd.double()).clamp(min=1e-6)
+
+
+def _view_aggregate_takes_16_byte_form(S, H, W):
+    return (H * W) % 4 == 0 and 2 <= S <= 11
+
+
+@pytest.mark.parametrize("B,S,G,D,H,W", [
+    (2, 3, 4, 5, 32, 36),       # 288 pixel quads: a second, partial blockIdx.x; GD = 20: a full strip of 16 and one of 4
+    (3, 11, 1, 17, 33, 32),     # 264 pixel quads; GD = 17: a strip of 1; the last case of the template switch
+    (2, 2, 4, 8, 20, 24),       # the first case of the template switch
+    (1, 12, 2, 3, 8, 8), (1, 1, 2, 3, 8, 8),      # element-wise kernel by S
+    (3, 4, 2, 3, 19, 23),       # element-wise kernel by HW % 4; workgroups straddle planes and batch items
+    (2, 3, 4, 6, 5, 7), (2, 5, 4, 19, 6, 10), (2, 2, 4, 19, 4, 4), (2, 11, 4, 19, 3, 8)])
+def test_view_aggregate(ops, B, S, G, D, H, W, monkeypatch):
+    monkeypatch.setattr(ops, "debug_fill", float("nan"))      # a (group, depth) plane that no strip writes shows as NaN
     cor, w = rnd(B, S, G, D, H, W, seed=1), rnd(B, S, H, W, seed=2, lo=0, hi=1)
-    want = (cor * w.view(B, S, 1, 1, H, W)).sum(1) / (1e-8 + w.sum(1)).view(B, 1, 1, H, W)
-    close(ops.view_aggregate(*dev(ops, cor, w)), want, 1e-5)
-    # planes of 16-byte multiples take the 16-byte form (a lane = 4 pixels x a strip of (group, depth) planes): same operations in the
-    # same order as the element-wise kernel, which a view of the same data at a 4-byte offset still takes
-    for S2, H2, W2 in ((5, 6, 10), (2, 4, 4), (11, 3, 8)):
-        cor2, w2 = rnd(B, S2, G, 19, H2, W2, seed=11), rnd(B, S2, H2, W2, seed=12, lo=0, hi=1)
-        want2 = (cor2 * w2.view(B, S2, 1, 1, H2, W2)).sum(1) / (1e-8 + w2.sum(1)).view(B, 1, 1, H2, W2)
-        a = ops.view_aggregate(*dev(ops, cor2, w2))
-        close(a, want2, 1e-5)
-        off = dev(ops, torch.cat([torch.zeros(1), cor2.flatten()]))[1:].view(cor2.shape)      # 4-byte offset: element-wise kernel
-        assert torch.equal(a.cpu(), ops.view_aggregate(off, dev(ops, w2)).cpu())
-    x = rnd(B * S, D, H, W, seed=3) * 3
-    close(ops.sigmoid_max_d(dev(ops, x)), torch.sigmoid(x).max(1)[0], 1e-6)
-    # depth regression (module.py:553-571)
+    zy, zx = H // 2, W - 3
+    w[:, :, zy, zx] = 0.0       # every view weight 0: 0 / 1e-8 = 0, finite
+    want = (cor.double() * w.double().view(B, S, 1, 1, H, W)).sum(1) / (1e-8 + w.double().sum(1)).view(B, 1, 1, H, W)
+    got = ops.view_aggregate(*dev(ops, cor, w))
+    err64("view_aggregate", got, want, 1e-5)
+    assert torch.equal(got.cpu()[..., zy, zx], torch.zeros(B, G, D))
+    if _view_aggregate_takes_16_byte_form(S, H, W):
+        # planes of 16-byte multiples take the 16-byte form (a lane = 4 pixels x a strip of (group, depth) planes): same operations in the
+        # same order as the element-wise kernel, which a view of the same data at a 4-byte offset still takes
+        assert dev(ops, cor).data_ptr() % 16 == 0
+        assert torch.equal(got.cpu(), ops.view_aggregate(_at_4_byte_offset(ops, cor), dev(ops, w)).cpu())
+        assert torch.equal(got.cpu(), ops.view_aggregate(dev(ops, cor), _at_4_byte_offset(ops, w)).cpu())
+
+
+@pytest.mark.parametrize("N,D,H,W", [(5, 7, 19, 23), (5, 1, 19, 23), (6, 6, 5, 7)])
+def test_sigmoid_max_d(ops, N, D, H, W):
+    x = rnd(N, D, H, W, seed=3) * 30
+    x[N - 1, :, 2, 3] = float("-inf")       # an empty column: sigmoid(-inf) = 0
+    x[1, D // 2, H - 1, W - 1] = float("inf")
+    want = torch.sigmoid(x.double()).max(1)[0]
+    assert want[N - 1, 2, 3] == 0 and want[1, H - 1, W - 1] == 1
+    got = ops.sigmoid_max_d(dev(ops, x))
+    err64("sigmoid_max_d", got, want, 1e-6)
+    assert got[N - 1, 2, 3] == 0 and got[1, H - 1, W - 1] == 1
+
+
+@pytest.mark.parametrize("B,D,H,W", [(3, 48, 19, 23), (1, 96, 16, 20), (2, 8, 17, 31), (2, 2, 9, 30), (2, 6, 5, 7)])
+def test_depth_regress(ops, B, D, H, W):
+    """soft-argmax depth regression and the 4-bin confidence around floor(index) (module.py:553-571).
+
+    The confidence is discontinuous where the regressed index crosses an integer: only pixels whose fp64 index lies within
+    1e-5 * D of an integer are left out (several times the fp32 error of the index), every other pixel must agree."""
     logits = rnd(B, D, H, W, seed=4) * 4
-    lo, hi = torch.tensor([1 / 935.0, 1 / 800.0]), torch.tensor([1 / 425.0, 1 / 500.0])
-    prob = F.softmax(logits, 1)
-    index = (torch.arange(D).view(1, D, 1, 1) * prob).sum(1, keepdim=True)
+    logits[0, :, 1, :] = -20.0          # index ~0.5, k = 0: the window k-1 .. k+2 is clipped below
+    logits[0, 0:2, 1, :] = 5.0
+    logits[B - 1, :, H - 2, :] = -20.0      # k = D-2: clipped above
+    logits[B - 1, D - 2, H - 2, :] = 5.5
+    logits[B - 1, D - 1, H - 2, :] = 5.0
+    lo, hi = _disp_range(B)
+    prob = F.softmax(logits.double(), 1)
+    index = (torch.arange(D, dtype=torch.float64).view(1, D, 1, 1) * prob).sum(1, keepdim=True)
     nd = index / (D - 1.0)
-    depth = O.disp_to_depth(nd, (1 / hi).view(-1, 1, 1, 1), (1 / lo).view(-1, 1, 1, 1))[1].squeeze(1)
+    depth = _disp_to_depth64(nd, lo, hi).squeeze(1)
     padded = F.pad(prob, (0, 0, 0, 0, 1, 2))
     sum4 = padded[:, 0:D] + padded[:, 1:D + 1] + padded[:, 2:D + 2] + padded[:, 3:D + 3]
-    conf = torch.gather(sum4, 1, index.long().clamp(0, D - 1))
-    g_nd, g_depth, g_conf = ops.depth_regress(*dev(ops, logits, 1 / (1 / lo), 1 / (1 / hi)))
-    close(g_nd, nd, 1e-5)
-    close(g_depth, depth, 1e-5)
-    assert float(((g_conf.cpu() - conf).abs() > 1e-4).float().mean()) < 0.05
-    # convex upsampling (module.py:237-248) for both ratios
-    for r in (2, 4):
-        inv, mask = rnd(B, 1, H, W, seed=5, lo=0, hi=1), rnd(B, 9 * r * r, H, W, seed=6) * 2
-        up = O.upsample_depth(inv, mask, r)
-        g_inv, g_depth = ops.convex_upsample(*dev(ops, inv, mask, 1 / (1 / lo), 1 / (1 / hi)), r)
-        close(g_inv, up, 1e-5)
-        close(g_depth, O.disp_to_depth(up.unsqueeze(1), (1 / hi).view(-1, 1, 1, 1), (1 / lo).view(-1, 1, 1, 1))[1].squeeze(1), 1e-5)
-    # depth <-> disp
+    k = index.long().clamp(0, D - 1)
+    conf = torch.gather(sum4, 1, k)
+    assert (k[0, 0, 1] == 0).all() and (k[B - 1, 0, H - 2] == D - 2).all()
+    g_nd, g_depth, g_conf = ops.depth_regress(*dev(ops, logits, lo, hi))
+    err64("depth_regress norm_depth", g_nd, nd, 1e-5)
+    err64("depth_regress depth", g_depth, depth, 1e-5)
+    excluded = (index - index.round()).abs() < 1e-5 * D
+    share = float(excluded.double().mean())
+    print(f"depth_regress confidence: {int(excluded.sum())} of {excluded.numel()} pixels within 1e-5 * D of an integer index")
+    assert share <= 0.01
+    assert not excluded[0, 0, 1].any() and not excluded[B - 1, 0, H - 2].any()
+    g_conf = g_conf.cpu()
+    assert g_conf.shape == conf.shape and torch.isfinite(g_conf).all()
+    cerr = (g_conf.double() - conf).abs()[~excluded]
+    print(f"depth_regress confidence: max abs err vs fp64 {float(cerr.max()):.3e} away from integer crossings")
+    assert float(cerr.max()) <= 1e-5
+
+
+def _convex_upsample64(inv, mask, r):
+    """softmax over the 9 taps of every output pixel's mask, then the convex combination of the zero-padded 3 x 3 neighbourhood
+    (module.py:237-248), fp64: inv [B,1,H,W], mask [B,9*r*r,H,W] -> [B,rH,rW]"""
+    B, _, H, W = inv.shape
+    m = torch.softmax(mask.double().view(B, 9, r, r, H, W), 1)
+    p = F.pad(inv.double()[:, 0], (1, 1, 1, 1))
+    nb = torch.stack([p[:, ky:ky + H, kx:kx + W] for ky in range(3) for kx in range(3)], 1).view(B, 9, 1, 1, H, W)
+    return (m * nb).sum(1).permute(0, 3, 1, 4, 2).reshape(B, r * H, r * W)
+
+
+@pytest.mark.parametrize("B,H,W,r,mscale", [(3, 19, 23, 2, 2.0), (3, 19, 23, 4, 2.0), (2, 20, 24, 4, 2.0), (3, 19, 23, 4, 60.0),
+                                            (2, 5, 7, 2, 2.0), (2, 5, 7, 4, 2.0)])
+def test_convex_upsample(ops, B, H, W, r, mscale):
+    inv, mask = rnd(B, 1, H, W, seed=5, lo=0.5, hi=1), rnd(B, 9 * r * r, H, W, seed=6) * mscale      # inv >= 0.5: the zero border shows
+    lo, hi = _disp_range(B)
+    up = _convex_upsample64(inv, mask, r)
+    g_inv, g_depth = ops.convex_upsample(*dev(ops, inv, mask, lo, hi), r)
+    err64("convex_upsample inv", g_inv, up, 1e-5)
+    err64("convex_upsample depth", g_depth, _disp_to_depth64(up, lo, hi), 1e-5)
+    none, g_depth2 = ops.convex_upsample(*dev(ops, inv, mask, lo, hi), r, want_inv=False)
+    assert none is None and torch.equal(g_depth2.cpu(), g_depth.cpu())
+
+
+@pytest.mark.parametrize("B,H,W", [(3, 19, 23), (2, 5, 7)])
+def test_depth_convert(ops, B, H, W):
+    lo, hi = _disp_range(B)
+    l64, h64 = lo.double().view(B, 1, 1, 1), hi.double().view(B, 1, 1, 1)
     dep = rnd(B, 1, H, W, seed=7, lo=430, hi=900)
-    close(ops.depth_convert(*dev(ops, dep, 1 / (1 / lo), 1 / (1 / hi)), 0),
-          O.depth_to_disp(dep, (1 / hi).view(-1, 1, 1, 1), (1 / lo).view(-1, 1, 1, 1)), 1e-5)
-    # refinement bookkeeping
-    inv, dl, upd = rnd(B, 1, H, W, seed=8, lo=0, hi=1), rnd(B, 1, H, W, seed=9), rnd(B, 1, H, W, seed=10)
-    new = (inv + 0.5 * dl + upd).clamp(0, 1)
-    big = dev(ops, torch.zeros(B, 3, H, W))
-    g_delta, g_new = ops.delta_update(*dev(ops, inv, dl, upd), 0.5, new2=big, new2_cstride=3, new2_coffset=2)
-    close(g_new, new, 1e-6)
-    close(g_delta, new - inv, 1e-6)
-    close(big[:, 2:3], new, 1e-6)
-    g_delta, g_new = ops.delta_update(*dev(ops, inv, dl), None, 0.5)
-    close(g_new, (inv + 0.5 * dl).clamp(0, 1), 1e-6)
-    # slices / resampling / layout
-    x = rnd(B, 9, H, W, seed=11)
-    close(ops.act_slice(dev(ops, x), K.ACT_TANH, 2, 4), torch.tanh(x[:, 2:6]), 1e-6)
-    close(ops.upsample_nearest(dev(ops, x), 4), F.interpolate(x, scale_factor=4, mode="nearest"), 0)
-    for f, xs in ((2, x), (8, x), (3, x), (2, x[..., :7].contiguous())):      # 16-byte rows (4 outputs per lane) and the ragged fallback (odd row lengths)
-        close(ops.upsample_nearest(dev(ops, xs), f), F.interpolate(xs, scale_factor=f, mode="nearest"), 0)
+    g_disp = ops.depth_convert(*dev(ops, dep, lo, hi), K._lib.EW_DEPTH_TO_DISP)
+    err64("depth_convert depth -> disp", g_disp, (1.0 / dep.double() - l64) / (h64 - l64), 1e-5)
+    disp = rnd(B, 1, H, W, seed=8, lo=0, hi=1)
+    g_dep = ops.depth_convert(*dev(ops, disp, lo, hi), K._lib.EW_DISP_TO_DEPTH)
+    err64("depth_convert disp -> depth", g_dep, _disp_to_depth64(disp, lo, hi), 1e-5)
+    back = ops.depth_convert(g_disp, *dev(ops, lo, hi), K._lib.EW_DISP_TO_DEPTH).cpu()
+    rel = float(((back.double() - dep.double()) / dep.double()).abs().max())
+    print(f"depth_convert depth -> disp -> depth: max rel err {rel:.3e}")
+    assert rel <= 1e-5
+
+
+@pytest.mark.parametrize("B,H,W,cstride,coffset", [(3, 19, 23, 5, 3), (2, 5, 7, 3, 2)])
+def test_delta_update(ops, B, H, W, cstride, coffset):
+    """refinement bookkeeping: new = clamp(inv + scale * delta (+ update), 0, 1), delta_out = new - inv, new mirrored into a channel slice"""
+    inv, dl, upd = rnd(B, 1, H, W, seed=8, lo=0, hi=1), rnd(B, 1, H, W, seed=9) * 2, rnd(B, 1, H, W, seed=10)
+    for u in (upd, None):
+        raw = inv.double() + 0.5 * dl.double() + (u.double() if u is not None else 0.0)
+        assert float((raw < 0).double().mean()) >= 0.1 and float((raw > 1).double().mean()) >= 0.1      # both ends of the clamp
+        new = raw.clamp(0, 1)
+        big = dev(ops, torch.full((B, cstride, H, W), _SENTINEL))
+        g_delta, g_new = ops.delta_update(*dev(ops, inv, dl, u), 0.5, new2=big, new2_cstride=cstride, new2_coffset=coffset)
+        err64("delta_update new", g_new, new, 1e-6)
+        err64("delta_update delta", g_delta, new - inv.double(), 1e-6)
+        assert torch.equal(g_delta.cpu(), g_new.cpu() - inv)
+        big = big.cpu()
+        assert torch.equal(big[:, coffset:coffset + 1], g_new.cpu())
+        others = [c for c in range(cstride) if c != coffset]
+        assert (big[:, others] == _SENTINEL).all()
+    g_delta, g_new = ops.delta_update(*dev(ops, inv, dl), None, 0.5)      # no mirror
+    err64("delta_update new, no mirror", g_new, (inv.double() + 0.5 * dl.double()).clamp(0, 1), 1e-6)
+
+
+ACTS64 = {K.ACT_NONE: lambda x: x, K.ACT_RELU: lambda x: x.clamp(min=0), K.ACT_SIGMOID: lambda x: 1 / (1 + torch.exp(-x)),
+          K.ACT_TANH: torch.tanh, K.ACT_SILU: lambda x: x / (1 + torch.exp(-x))}
+
+
+@pytest.mark.parametrize("act", sorted(ACTS64))
+def test_act_slice(ops, act):
+    B, C, H, W, c_from, c_count, ocs, oco = 3, 9, 19, 23, 2, 4, 7, 2
+    x = rnd(B, C, H, W, seed=11) * 3
+    want = ACTS64[act](x[:, c_from:c_from + c_count].double())
+    err64("act_slice", ops.act_slice(dev(ops, x), act, c_from, c_count), want, 1e-6)
+    big = dev(ops, torch.full((B, ocs, H, W), _SENTINEL))
+    ret = ops.act_slice(dev(ops, x), act, c_from, c_count, out=big, out_cstride=ocs, out_coffset=oco)
+    assert ret.data_ptr() == big.data_ptr()
+    big = big.cpu()
+    err64("act_slice into a channel slice", big[:, oco:oco + c_count], want, 1e-6)
+    assert (big[:, :oco] == _SENTINEL).all() and (big[:, oco + c_count:] == _SENTINEL).all()
+
+
+@pytest.mark.parametrize("N,H,W,f,out_offset", [
+    (6, 19, 24, 4, False),      # 16-byte stores, 43776 quads: many workgroups
+    (3, 5, 4, 3, False),        # W * f = 12: a 16-byte store spans source pixels unevenly
+    (2, 7, 8, 8, False),
+    (2, 9, 7, 2, False),        # W * f = 14: element-wise kernel
+    (4, 6, 10, 2, False),       # W * f = 20: a 16-byte store holds two source pixels twice each
+    (6, 19, 24, 4, True),       # 16-byte rows, destination at a 4-byte offset: element-wise kernel
+    (18, 5, 7, 4, False), (18, 5, 7, 2, False), (18, 5, 7, 8, False), (18, 5, 7, 3, False)])
+def test_upsample_nearest(ops, N, H, W, f, out_offset):
+    x = rnd(N, H, W, seed=12)
+    want = F.interpolate(x[None], scale_factor=f, mode="nearest")[0]
+    if not out_offset:
+        close(ops.upsample_nearest(dev(ops, x), f), want, 0)
+        return
+    store = dev(ops, torch.full((want.numel() + 1,), _SENTINEL))
+    out = store[1:].view(want.shape)
+    assert out.data_ptr() % 16 == 4
+    ops._call("dmvs_upsample_nearest_f32", K._ptr(dev(ops, x)), K._ptr(out), N, H, W, f, ops.stream())
+    close(out, want, 0)
+    assert float(store[0]) == _SENTINEL
+
+
+@pytest.mark.parametrize("B,C,H,W", [(3, 5, 19, 23), (2, 3, 20, 24), (2, 9, 5, 7)])
+def test_nchw_to_nhwc(ops, B, C, H, W):
+    x = rnd(B, C, H, W, seed=13)
     close(ops.nchw_to_nhwc(dev(ops, x)), x.permute(0, 2, 3, 1).contiguous(), 0)
+
+
+def test_compose_proj_second_workgroup(ops):
+    """72 (batch item, source view) pairs: a second 64-lane workgroup; against numpy fp64"""
+    B, V = 9, 9
+    pm = _cams(B, V, 16, 20, 1)
+    out = ops.compose_proj(dev(ops, pm)).cpu()
+    assert out.shape == (B, V - 1, 12)
+    p64 = pm.numpy().astype(np.float64)
+    cam = p64[:, :, 0].copy()       # E with its top 3 x 4 replaced by K @ E[:3, :4]
+    cam[:, :, :3, :4] = p64[:, :, 1, :3, :3] @ p64[:, :, 0, :3, :4]
+    m = torch.from_numpy(cam[:, 1:] @ np.linalg.inv(cam[:, :1]))       # [B, S, 4, 4]
+    for s in range(V - 1):
+        err64(f"compose_proj rotation, view {s + 1}", out[:, s, :9].reshape(B, 3, 3), m[:, s, :3, :3], 1e-6)
+        terr, tscale = float((out[:, s, 9:].double() - m[:, s, :3, 3]).abs().max()), float(m[:, s, :3, 3].abs().max())
+        print(f"compose_proj translation, view {s + 1}: max abs err vs fp64 {terr:.3e} (scale {tscale:.3e})")
+        assert terr < 1e-3 * tscale
 
 
 @pytest.mark.parametrize("C,HW", [(16, (9, 13)), (32, (40, 70))])
@@ -683,6 +853,66 @@ def test_groupnorm_silu(ops, C, HW):
     want = F.silu(y * (ss[:, :C, None, None] + 1) + ss[:, C:, None, None]) + res
     close(ops.groupnorm_silu(*dev(ops, x, gamma, beta), 4, scale_shift=dev(ops, ss), residual=dev(ops, res)), want, 2e-5)
     close(ops.groupnorm_silu(*dev(ops, x, gamma, beta), 4), F.silu(y), 2e-5)
+
+
+def _groupnorm_silu64(x, gamma, beta, groups, ss=None, res=None, eps=1e-5):
+    """silu(GroupNorm(x) * (scale + 1) + shift) (+ residual) in fp64 from fp32 inputs, biased variance"""
+    B, C, H, W = x.shape
+    xg = x.double().view(B, groups, -1)
+    mean, var = xg.mean(-1, keepdim=True), xg.var(-1, unbiased=False, keepdim=True)
+    y = ((xg - mean) / torch.sqrt(var + eps)).view(B, C, H, W) * gamma.double().view(1, C, 1, 1) + beta.double().view(1, C, 1, 1)
+    if ss is not None:
+        y = y * (ss.double()[:, :C, None, None] + 1) + ss.double()[:, C:, None, None]
+    y = y / (1 + torch.exp(-y))
+    return y if res is None else y + res.double()
+
+
+@pytest.mark.parametrize("H,W,extras,offset", [
+    (50, 82, False, None), (50, 82, True, None),        # 4100: 16-byte form, a second blockIdx.x of 4 elements; per_group = 8200: a second statistics chunk of 8
+    (17, 241, False, None), (17, 241, True, None),      # 4097: element-wise form, a second block of 1 element
+    (50, 82, False, "x"), (50, 82, True, "x"), (50, 82, True, "residual")])      # a 4-byte offset operand: element-wise form on 16-byte planes
+def test_groupnorm_silu_planes(ops, H, W, extras, offset):
+    B, C, groups = 2, 8, 4
+    x = rnd(B, C, H, W, seed=1) * 2 + 0.3
+    gamma, beta = rnd(C, seed=2, lo=0.5, hi=1.5), rnd(C, seed=3)
+    ss, res = (rnd(B, 2 * C, seed=4), rnd(B, C, H, W, seed=5)) if extras else (None, None)
+    want = _groupnorm_silu64(x, gamma, beta, groups, ss, res)
+    xd, gd, bd, sd, rd = dev(ops, x, gamma, beta, ss, res)
+    got = ops.groupnorm_silu(xd, gd, bd, groups, scale_shift=sd, residual=rd)
+    err64("groupnorm_silu", got, want, 2e-5)
+    # the same into a caller's slice of a larger tensor
+    big = dev(ops, torch.full((B + 2, C, H, W), _SENTINEL))
+    ret = ops.groupnorm_silu(xd, gd, bd, groups, scale_shift=sd, residual=rd, out=big[1:B + 1])
+    assert ret.data_ptr() == big[1:].data_ptr()
+    assert torch.equal(big[1:B + 1].cpu(), got.cpu())
+    assert (big[0] == _SENTINEL).all() and (big[B + 1] == _SENTINEL).all()
+    # groupnorm_apply: the second pass alone, from the statistics of the first
+    _, stats = ops.groupnorm_silu_train(xd, gd, bd, groups, scale_shift=sd)
+    big.fill_(_SENTINEL)
+    ops.groupnorm_apply(xd, gd, bd, groups, stats, scale_shift=sd, residual=rd, out=big[1:B + 1])
+    assert torch.equal(big[1:B + 1].cpu(), got.cpu())
+    assert (big[0] == _SENTINEL).all() and (big[B + 1] == _SENTINEL).all()
+    if offset:
+        assert (H * W) % 4 == 0 and xd.data_ptr() % 16 == 0
+        xo = _at_4_byte_offset(ops, x) if offset == "x" else xd
+        ro = _at_4_byte_offset(ops, res) if offset == "residual" else rd
+        assert torch.equal(ops.groupnorm_silu(xo, gd, bd, groups, scale_shift=sd, residual=ro).cpu(), got.cpu())
+        assert torch.equal(ops.groupnorm_apply(xo, gd, bd, groups, stats, scale_shift=sd, residual=ro).cpu(), got.cpu())
+
+
+def test_groupnorm_silu_large_mean(ops):
+    """input mean 30, standard deviation 1: var = E[x^2] - mean^2 cancels three digits.  The bound is the error of fp32
+    F.group_norm + F.silu against the same fp64 reference, times 4 for a different summation order."""
+    B, C, H, W, groups = 2, 8, 50, 82, 4
+    x = torch.from_numpy(np.random.RandomState(7).standard_normal((B, C, H, W)).astype(np.float32)) + 30.0
+    gamma, beta = rnd(C, seed=2, lo=0.5, hi=1.5), rnd(C, seed=3)
+    want = _groupnorm_silu64(x, gamma, beta, groups)
+    err_torch = float((F.silu(F.group_norm(x, groups, gamma, beta, 1e-5)).double() - want).abs().max())
+    got = ops.groupnorm_silu(*dev(ops, x, gamma, beta), groups).cpu()
+    assert torch.isfinite(got).all()
+    err = float((got.double() - want).abs().max())
+    print(f"groupnorm_silu, mean 30 / std 1: max abs err vs fp64 {err:.3e}; fp32 F.group_norm + F.silu {err_torch:.3e}")
+    assert err <= 4 * err_torch
 
 
 @pytest.mark.parametrize("cin,cout,HW", [(16, 16, (21, 37)), (48, 32, (16, 16)), (8, 8, (9, 50))])
