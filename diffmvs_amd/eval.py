@@ -46,6 +46,7 @@ def run_scenes(model, a, scenes, device):
     for bit (tests/test_scene.py); the timed region is the model call like test.py:122-127 -- the store's one-off cost is reported
     per scene in `feature_store_s`."""
     times, report, store_s = [], {}, {}
+    sync = torch.cuda.synchronize if torch.device(device).type == "cuda" else (lambda: None)
     first_calls, seen_geometry = [], set()      # with HIP graphs the first call of an input geometry = two warm-up forwards + the capture
     for scene in scenes:
         ds = IO.MVSDataset(a.testpath, a.num_view, a.numdepth, dataset=a.dataset, scan=[scene], max_h=a.max_h, max_w=a.max_w)
@@ -54,11 +55,11 @@ def run_scenes(model, a, scenes, device):
             ids = sorted({v for i in range(len(ds)) for v in ds.view_ids(i)})
             views = {v: ds.load_view(scene, v) for v in ids}
             if len({views[v][0].shape for v in ids}) == 1:          # (a general dataset whose images differ in size cannot be stacked)
-                torch.cuda.synchronize()
+                sync()
                 t0 = time.time()
                 stack = torch.from_numpy(np.stack([np.ascontiguousarray(views[v][0].transpose(2, 0, 1)) for v in ids]))
                 store = model.scene_features(stack.to(device))
-                torch.cuda.synchronize()
+                sync()
                 store_s[scene] = time.time() - t0
                 row_of = {v: r for r, v in enumerate(ids)}
         errs = []
@@ -70,14 +71,14 @@ def run_scenes(model, a, scenes, device):
             dv = sample["depth_values"].to(device)
             if store is not None:
                 feats_ids = torch.tensor([[row_of[v] for v in ds.view_ids(i)] for i in idxs])
-            torch.cuda.synchronize()
+            sync()
             t0 = time.time()
             with torch.no_grad():
                 if store is not None:
                     out = model(imgs[:1], proj, dv, feats=store.gather(feats_ids))
                 else:
                     out = model(imgs, proj, dv)
-            torch.cuda.synchronize()
+            sync()
             geom = (tuple(imgs[0].shape), len(imgs), store is not None)
             if model.hip_graphs and geom not in seen_geometry:
                 first_calls.append(time.time() - t0)             # reported on its own: not comparable to test.py:122-127's per-view time
@@ -99,7 +100,8 @@ def run_scenes(model, a, scenes, device):
     return times, report, store_s
 
 
-def main(argv=None):
+def main(argv=None, device=None):
+    """device: None = this rank's HIP device (the command line); the tests pass the host emulation's"""
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--testpath", required=True)
     ap.add_argument("--dataset", default="dtu", choices=["dtu", "tank", "eth3d", "general"])
@@ -132,6 +134,9 @@ def main(argv=None):
     ap.add_argument("--cloud_max_dist", type=float, default=20.0, help="--gt_ply: distances are clamped here (DTU: 20)")
     ap.add_argument("--cloud_density", type=float, default=None, help="--gt_ply: thin the fused cloud to one point per voxel of this side (DTU: 0.2)")
     ap.add_argument("--cloud_thresholds", type=float, nargs="*", default=[1.0, 2.0, 5.0], help="--gt_ply: F-score thresholds")
+    ap.add_argument("--gt_depth", default=None, help="tree with <scan>/depth_gt/%%08d.pfm (+ optional mask/%%08d.png): score the written depth maps against "
+                    "it with diffmvs_amd.depth_eval (integer sums on the GPU); adds depth_metrics to the result, writes nothing")
+    ap.add_argument("--depth_thresholds", type=float, nargs="*", default=[2.0, 4.0, 8.0], help="--gt_depth: absolute-error inlier thresholds")
     ap.add_argument("--scene_cache", type=int, default=1, choices=[0, 1],
                     help="1 (default): every image of a scene through FeatureNet once, features resident in HBM; 0: the reference's per-sample order")
     ap.add_argument("--graphs", type=int, default=None, choices=[0, 1],
@@ -144,8 +149,9 @@ def main(argv=None):
     a = ap.parse_args(argv)
 
     rank, world, local = shard.env_rank_world()
-    torch.cuda.set_device(local)
-    device = torch.device("cuda", local)
+    if device is None:
+        torch.cuda.set_device(local)
+        device = torch.device("cuda", local)
     torch.manual_seed(a.seed + rank)
     from models import CasDiffMVS
     model = CasDiffMVS(build_args(a), test=True).eval()
@@ -192,6 +198,11 @@ def main(argv=None):
                 res.setdefault("cloud_metrics", {})[scene] = cloud_eval.evaluate_files(
                     Ops.for_device(device), kw["plyfilename"], a.gt_ply.replace("{scene}", scene), a.cloud_max_dist, a.cloud_thresholds,
                     density=a.cloud_density, **extra)
+    if a.gt_depth:
+        from . import depth_eval
+        from .ops import Ops
+        res["depth_metrics"] = depth_eval.score_tree(Ops.for_device(device), a.outdir, a.gt_depth, mine, a.depth_thresholds)
+        depth_eval.warn_hidden(res["depth_metrics"]["overall"], a.outdir)
     print(json.dumps(res), flush=True)
     return res
 

@@ -866,3 +866,23 @@ class Ops:
         self._call("dmvs_cloud_crop_prism_f32", _ptr(points), int(points.shape[0]), self._transform_arg(transform), _ptr(polygon), K, int(axis),
                    float(axis_min), float(axis_max), _ptr(out), self.stream())
         return out
+
+    # ------------------------------------------------------------------ depth-map scoring (diffmvs_amd/depth_eval.py)
+    def depth_stats(self, est, gt, mask, thresholds, big, scale, band=None, blocks=0):
+        """dmvs_depth_stats_f32 -> [B, 7 + T] int64 on the device, one row per batch item: masked pixels, scored pixels, pixels left out
+        (non-finite est / gt or gt <= 0), clamped terms, the fixed-point sums of |e|, |e| / gt and e^2, and per threshold the scored pixels
+        with |e| < threshold (include/dmvs.h).  est, gt [B,H,W] fp32; mask None or [B,H,W] fp32 (> 0.5 = in); band None or (lo, hi)."""
+        self._chk_typed("depth_stats", (est, torch.float32), (gt, torch.float32), (mask, torch.float32))
+        T = len(thresholds)
+        if T > _lib.DEPTH_MAX_THRESHOLDS:
+            raise _lib.DmvsError(f"depth_stats: {T} thresholds; at most {_lib.DEPTH_MAX_THRESHOLDS} are supported")
+        if est.dim() != 3 or gt.shape != est.shape or (mask is not None and mask.shape != est.shape):
+            raise _lib.DmvsError(f"depth_stats: est, gt and the mask must share one [B,H,W] shape, got {tuple(est.shape)}, {tuple(gt.shape)}"
+                                 + (f", {tuple(mask.shape)}" if mask is not None else ""))
+        B, HW = int(est.shape[0]), int(est.shape[1] * est.shape[2])
+        out = torch.empty(B, _lib.DEPTH_SLOTS + T, dtype=torch.int64, device=self.device)
+        thr = (C.c_float * max(1, T))(*[float(t) for t in thresholds])
+        lo, hi = (0.0, float("inf")) if band is None else (float(band[0]), float(band[1]))
+        self._call("dmvs_depth_stats_f32", _ptr(est), _ptr(gt), _ptr(mask), B, HW, thr, T, lo, hi, float(big), float(scale), int(blocks),
+                   _ptr(out), self.stream())
+        return out

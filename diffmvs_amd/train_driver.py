@@ -19,7 +19,21 @@ What changes against the reference when the batch is spread over processes inste
   * rank 0 writes `<logdir>/model_{epoch:06d}.ckpt` = {'epoch', 'model', 'optimizer'} every --save_freq epochs; --resume loads the
     highest-numbered one on every rank (train.py:330-339) and continues the LR schedule where it stopped.
 Samples follow the dict contract of the reference's training datasets (datasets/dtu.py:196-210: imgs, proj_matrices, depth_values, depth
-and mask per stage); `TreeTrainSet` reads them from an MVS tree with ground-truth depth maps, `SyntheticTrainSet` renders them."""
+and mask per stage); `TreeTrainSet` reads them from an MVS tree with ground-truth depth maps, `SyntheticTrainSet` renders them.
+
+Validation (train.py:144-162, :234-291): with --valpath / --vallist or --val_synthetic N a held-out pass runs after the checkpoint step of every
+--eval_freq-th epoch and of the last one (`validate`): model.eval(), no_grad, the eval forward of the current weights, the initial depth scored
+against stage1 (`init_abs_depth_error`) and the final depth against stage4 (`final_depth_error`, plus abs-rel, RMSE and inlier shares) by
+diffmvs_amd.depth_eval -- integer rows per sample.  Determinism rules: samples are dealt rank-strided in index order, nothing is dropped, the source
+views are the first val_views - 1 of the pair list (no draw), the diffusion noise of sample i comes from a host generator seeded by (seed, i)
+alone and the batch tensor is assembled item by item, the ranks all_gather (sample index, integer rows) and the summary is computed from the rows
+sorted by index: the record is the same for any world size and any --val_batch_size.  Rank 0 appends it to <logdir>/val.jsonl (with
+`best_epoch`, the epoch of the lowest final_depth_error so far; no extra *.ckpt is written -- --resume parses every *.ckpt name as an epoch).
+The pass uses its own generators, leaves the global RNG alone, keeps HIP graphs off, and puts model.train() and the epoch's stream hooks back.
+The reference also reports the LOSS of the held-out batch.  This pass does not, although it could: the eval forward of a `test=False` model
+returns every iterate in "depth" and the Unet confidences in "conf" (diffmvs_amd.engine.Engine.forward), which is what compute_inverse_loss
+takes.  It is left out because that loss is an fp32 mean over the batch: to keep the record independent of --val_batch_size and of the
+world size it would have to be evaluated sample by sample and reduced like the rows, which nobody has asked for yet."""
 from __future__ import annotations
 
 import argparse
@@ -57,7 +71,8 @@ class SyntheticTrainSet:
                 self._cache.clear()
             self._cache[idx] = synth.synth_inputs(self.H, self.W, self.pool, B=1, seed=self.seed + idx, numdepth=self.numdepth, with_gt=True)
         imgs, proj, dv, gt, mask = self._cache[idx]
-        ids = [0] + sorted(rng.sample(range(1, self.pool + 1), self.nviews - 1))          # datasets/dtu.py:125
+        # datasets/dtu.py:125; rng None (validation): no draw, the first nviews - 1 source views
+        ids = [0] + (list(range(1, self.nviews)) if rng is None else sorted(rng.sample(range(1, self.pool + 1), self.nviews - 1)))
         return {"imgs": [imgs[v][0] for v in ids], "proj_matrices": {k: p[0, ids] for k, p in proj.items()}, "depth_values": dv[0],
                 "depth": {k: g[0] for k, g in gt.items()}, "mask": {k: m[0] for k, m in mask.items()}, "index": idx, "view_ids": ids}
 
@@ -82,7 +97,8 @@ class TreeTrainSet:
     def get(self, idx: int, rng: random.Random) -> dict:
         i, base = self.items[idx]
         scan, ref, srcs = self.ds.metas[i]
-        ids = [ref] + rng.sample(list(srcs), self.nviews - 1)                             # datasets/dtu.py:125
+        # datasets/dtu.py:125; rng None (validation): no draw, the first nviews - 1 of the pair list
+        ids = [ref] + (list(srcs)[:self.nviews - 1] if rng is None else rng.sample(list(srcs), self.nviews - 1))
         loaded = [self.ds.load_view(scan, v) for v in ids]
         s = IO.make_sample([x[0] for x in loaded], [x[1] for x in loaded], [x[2] for x in loaded], loaded[0][3], loaded[0][4], self.ds.numdepth)
         depth = np.ascontiguousarray(IO.read_pfm(os.path.join(base, "depth_gt", f"{ref:08d}.pfm"))[0]).astype(np.float32)
@@ -162,6 +178,103 @@ class RankStreams:
         model.t_source, model.noise_source = self.t_source, self.noise_source
 
 
+# ------------------------------------------------------------------------------------------ validation
+VAL_THRESHOLDS = (2.0, 4.0, 8.0)
+
+
+class SampleNoise:
+    """The diffusion noise of a validation batch: item b of every draw comes from a HOST generator seeded by (seed, sample index) alone, so
+    a sample sees the same noise in any batch, on any rank and on any device."""
+
+    def __init__(self, seed: int, idxs: Sequence[int]):
+        self.gens = [torch.Generator().manual_seed(((seed * 1000003 + i * 7919 + 5) ^ 0x5DEECE66D) & 0x7FFFFFFFFFFF) for i in idxs]
+
+    def __call__(self, shape, device):
+        if shape[0] != len(self.gens):
+            raise ValueError(f"noise for a batch of {shape[0]} asked of {len(self.gens)} sample streams")
+        return torch.stack([torch.randn(tuple(shape[1:]), generator=g) for g in self.gens]).to(device)
+
+
+def validate(model, ds, ops, device, seed: int = 0, batch_size: int = 1, rank: int = 0, world: int = 1, thresholds=VAL_THRESHOLDS) -> dict:
+    """One held-out pass over `ds` with the model's CURRENT weights (train.py:144-162, :234-291) -> the validation record without its
+    epoch / step / seconds, identical on every rank and for every (world, batch_size): see the module docstring.  Collective when world > 1.
+    Leaves the model as it found it: training flag, noise / t hooks, graph switch."""
+    from . import depth_eval
+    was_training, hooks, graphs = model.training, (model.noise_source, model.t_source), model.hip_graphs
+    width = depth_eval.HEAD + depth_eval.SLOTS + len(thresholds)
+    mine = list(range(rank, len(ds), world))                                               # rank-strided, in order, nothing dropped
+    rows, kept = [], []
+    try:
+        if world > 1:
+            # BatchNorm running statistics stay per rank while training and rank 0's are the ones saved: every rank validates the model
+            # the checkpoint holds, then takes its own statistics back
+            import torch.distributed as dist
+            for b in model.buffers():
+                kept.append(b.detach().clone())
+                dist.broadcast(b, src=0)
+        model.eval()
+        model.hip_graphs = False
+        with torch.no_grad():
+            for i0 in range(0, len(mine), batch_size):
+                idxs = mine[i0:i0 + batch_size]
+                batch = collate_train([ds.get(i, None) for i in idxs], device)
+                model.noise_source = SampleNoise(seed, idxs)
+                out = model(batch["imgs"], batch["proj_matrices"], batch["depth_values"])      # through model.engine(): re-packed after a step
+                big = (1.0 / batch["depth_values"][:, 0].double()).tolist()                 # the sample's depth_max
+                init = depth_eval.score(ops, out["depth"][0], batch["depth"]["stage1"], batch["mask"]["stage1"], thresholds, big=big)
+                final = depth_eval.score(ops, out["depth"][-1], batch["depth"]["stage4"], batch["mask"]["stage4"], thresholds, big=big)
+                index = torch.tensor(idxs, dtype=torch.int64, device=init.device)[:, None]
+                rows.append(torch.cat([index, init, final], 1))
+    finally:
+        with torch.no_grad():
+            for b, k in zip(model.buffers(), kept):
+                b.copy_(k)
+        model.noise_source, model.t_source = hooks
+        model.hip_graphs = graphs
+        model.train(was_training)
+    per_rank = (len(ds) + world - 1) // world
+    table = torch.full((per_rank, 1 + 2 * width), -1, dtype=torch.int64, device=ops.device)    # padded with index -1: equal sizes for the gather
+    if rows:
+        got = torch.cat(rows)
+        table[:got.shape[0]] = got
+    if world > 1:
+        import torch.distributed as dist
+        parts = [torch.empty_like(table) for _ in range(world)]
+        dist.all_gather(parts, table)
+        table = torch.cat(parts)
+    host = sorted((r for r in table.cpu().tolist() if r[0] >= 0), key=lambda r: r[0])          # the one readback; sample order
+    init = depth_eval.summarise([r[1:1 + width] for r in host], thresholds)
+    final = depth_eval.summarise([r[1 + width:] for r in host], thresholds)
+    rec = {"samples": len(host), "init_abs_depth_error": init["abs_err"], "final_depth_error": final["abs_err"], "final_abs_rel": final["abs_rel"],
+           "final_rmse": final["rmse"]}
+    rec.update({"final_" + k: v for k, v in final.items() if k.startswith("inlier_")})
+    rec.update(init=init, final=final)
+    return rec
+
+
+def build_val_dataset(a):
+    """the held-out set of --valpath / --vallist or --val_synthetic (None: no validation)"""
+    views = a.val_views or a.trainviews
+    if a.valpath:
+        scans = [""]
+        if a.vallist:
+            with open(a.vallist) as f:
+                scans = [ln.strip() for ln in f if ln.strip()]
+        return TreeTrainSet(a.valpath, scans, views, a.numdepth, dataset=a.dataset)
+    if a.val_synthetic:
+        # scene i of a synthetic set is rendered from seed + i: the held-out scenes start right past the last training scene
+        return SyntheticTrainSet(a.val_synthetic, a.height, a.width, views, pool=a.view_pool, seed=a.seed + max(a.synthetic, 0), numdepth=a.numdepth)
+    return None
+
+
+def _read_val_log(path: str, before_epoch: int) -> List[dict]:
+    if not os.path.exists(path):
+        return []
+    with open(path) as f:
+        recs = [json.loads(ln) for ln in f if ln.strip()]
+    return [r for r in recs if r.get("epoch", 0) < before_epoch]
+
+
 # ------------------------------------------------------------------------------------------ the loop
 def latest_checkpoint(logdir: str):
     """train.py:330-335: the highest-numbered *.ckpt of the log directory"""
@@ -194,10 +307,16 @@ def run(a, device=None, ops=None) -> dict:
     model = CasDiffMVS(margs, test=False)
     if a.loadckpt:
         model.load_state_dict(torch.load(a.loadckpt, map_location="cpu")["model"])             # train.py:340-344 (strict)
-    else:
+    elif a.init == "synthetic":
         model.load_state_dict(synth.synth_state_dict(model.state_dict(), 123 + (0 if a.same_init else rank)), strict=True)
+    # (--init default: the modules' own initialisation, like the reference's train.py; the Trainer broadcasts rank 0's)
     model.to(device)
     ds = build_dataset(a)
+    if a.eval_freq < 1 or a.val_batch_size < 1:
+        raise SystemExit(f"train_driver: --eval_freq {a.eval_freq} and --val_batch_size {a.val_batch_size} must be at least 1")
+    val_ds = build_val_dataset(a)
+    if val_ds is not None and len(val_ds) == 0:
+        raise SystemExit("train_driver: the validation set is empty (no reference view with depth_gt/ and enough source views)")
     sampler = RankStridedSampler(len(ds), rank, world, seed=a.seed)
     steps_per_epoch = len(sampler.batches(0, a.batch_size))
     if steps_per_epoch == 0:
@@ -218,6 +337,15 @@ def run(a, device=None, ops=None) -> dict:
         tr.step_count = steps_per_epoch * start_epoch                                          # the schedule continues where the epoch count says
     log = {"rank": rank, "world": world, "steps_per_epoch": steps_per_epoch, "start_epoch": start_epoch, "seen": [], "view_draws": [],
            "t_draws": [], "loss": [], "lr": []}
+    val_file = os.path.join(a.logdir, "val.jsonl")
+    if val_ds is not None:
+        log["val"] = []
+        # rank 0 owns the file (the other ranks may not even see it): it alone reads the earlier records and names the best epoch.  On
+        # --resume the records of epochs that are trained again are dropped, so the file holds every epoch once
+        earlier = _read_val_log(val_file, start_epoch) if a.resume and rank == 0 else []
+        if a.resume and rank == 0 and os.path.exists(val_file):
+            with open(val_file, "w") as f:
+                f.writelines(json.dumps(r) + "\n" for r in earlier)
     for epoch in range(start_epoch, a.epochs):
         streams = RankStreams(a.seed, rank, epoch, device)
         streams.install(model)
@@ -240,6 +368,34 @@ def run(a, device=None, ops=None) -> dict:
         if (epoch + 1) % a.save_freq == 0 and rank == 0:                                       # train.py:136-141
             os.makedirs(a.logdir, exist_ok=True)
             torch.save(tr.checkpoint(epoch), os.path.join(a.logdir, "model_{:0>6}.ckpt".format(epoch)))
+        if val_ds is not None and (epoch % a.eval_freq == 0 or epoch == a.epochs - 1):         # train.py:145
+            t0 = time.time()
+            rec = validate(model, val_ds, tr.ops, device, seed=a.seed, batch_size=a.val_batch_size, rank=rank, world=world)
+            streams.install(model)                                                             # (validate restored them; the epoch's hooks stay)
+            rec = {"epoch": epoch, "step": tr.step_count, **rec, "seconds": time.time() - t0}
+            best = None
+            if rank == 0:
+                known = [r for r in earlier + log["val"] + [rec] if r["final_depth_error"] is not None]
+                best = min(known, key=lambda r: (r["final_depth_error"], r["epoch"]))["epoch"] if known else None
+            if world > 1:
+                import torch.distributed as dist
+                box = [best]
+                dist.broadcast_object_list(box, src=0)
+                best = box[0]
+            rec["best_epoch"] = best
+            log["val"].append(rec)
+            if rank == 0:
+                os.makedirs(a.logdir, exist_ok=True)
+                with open(val_file, "a") as f:
+                    f.write(json.dumps(rec) + "\n")
+                fin = rec["final"]
+                hidden = "".join(f", {k} {v}" for k, v in (("left_out", rec["init"]["left_out"] + fin["left_out"]),
+                                                          ("saturated", rec["init"]["saturated"] + fin["saturated"]),
+                                                          ("empty_items", rec["init"]["empty_items"] + fin["empty_items"])) if v)
+                fmt = lambda v: "nan" if v is None else "{:.4f}".format(v)  # noqa: E731
+                print("Epoch {}/{}, validation on {} samples: init_abs_depth_error = {}, final_depth_error = {}, abs_rel = {}, best epoch {}{}, "
+                      "time = {:.3f}".format(epoch, a.epochs, rec["samples"], fmt(rec["init_abs_depth_error"]), fmt(rec["final_depth_error"]),
+                                             fmt(rec["final_abs_rel"]), rec["best_epoch"], hidden, rec["seconds"]), flush=True)
     flat = tr.flat.data.detach().double().cpu()
     log["weights_sum"], log["weights_abs_sum"], log["steps_done"] = float(flat.sum()), float(flat.abs().sum()), tr.step_count
     if world > 1:
@@ -274,6 +430,15 @@ def parse_args(argv=None):
     ap.add_argument("--lr_sche", default="onecycle", choices=["onecycle", "mslr", "const"])
     ap.add_argument("--lrepochs", default="10,12,14:2")
     ap.add_argument("--save_freq", type=int, default=1)
+    ap.add_argument("--init", default="synthetic", choices=["synthetic", "default"],
+                    help="initial weights without --loadckpt.  synthetic (default): synth.synth_state_dict, the seeded weights of this package's tests and "
+                         "benchmarks; default: the modules' own initialisation, as the reference's train.py -- what a REAL training run wants")
+    ap.add_argument("--valpath", default=None, help="held-out MVS tree with depth_gt/ (the layout of --trainpath): validate during training")
+    ap.add_argument("--vallist", default=None, help="scans of --valpath, one per line")
+    ap.add_argument("--val_synthetic", type=int, default=0, help="validate on this many rendered scenes (seeds disjoint from the training scenes')")
+    ap.add_argument("--eval_freq", type=int, default=1, help="validate every N-th epoch and after the last (train.py --eval_freq); needs a validation set")
+    ap.add_argument("--val_batch_size", type=int, default=1, help="per GPU; the validation record does not depend on it")
+    ap.add_argument("--val_views", type=int, default=None, help="images per validation sample (default: --trainviews); the first val_views - 1 of the pair list")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--same_init", type=int, default=1, help=argparse.SUPPRESS)       # 0: per-rank initial weights (test of the broadcast)
     ap.add_argument("--backend", default="nccl", help=argparse.SUPPRESS)

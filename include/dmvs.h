@@ -575,6 +575,35 @@ int dmvs_cloud_pair_moments_f64(const float* source, int64_t N, const double* tr
 int dmvs_cloud_crop_prism_f32(const float* points, int64_t N, const double* transform, const double* polygon, int32_t K,
                               int32_t axis, double axis_min, double axis_max, uint8_t* inside, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Depth-map scoring (added under ABI 4, additive): the per-pixel errors of utils.py:150-187 (AbsDepthError_metrics) and the "DTU abs-rel"
+ * of BASELINE.json as integer and fixed-point sums per batch item (diffmvs_amd/depth_eval.py turns the rows into the metrics).
+ *
+ * dmvs_depth_stats_f32: est, gt [B, HW] fp32;  mask: NULL (every pixel) or [B, HW] fp32, a pixel is masked in where mask > 0.5
+ *   (train.py:214-217).  out [B, DMVS_DEPTH_SLOTS + T] int64 (device, zeroed here), per item:
+ *     [0] pixels masked in
+ *     [1] pixels scored: masked in, est and gt finite, gt > 0, and band_lo <= |e| <= band_hi
+ *     [2] pixels left out because est or gt is not finite or gt <= 0  (masked in and inside the band but not scored: [0] - [1] - [2])
+ *     [3] TERMS of the three sums below that were clamped (|e| > big, |e| / gt > big, e^2 > big^2: up to three per scored pixel)
+ *     [4] sum llrint(min(|e|, big) * scale)            [5] sum llrint(min(|e| / gt, big) * scale)
+ *     [6] sum llrint(min(e^2, big^2) * scale_sq)       [7 + t] scored pixels with |e| < (double)thresholds[t]
+ *   over the scored pixels, with e = (double)est - (double)gt; the difference, the quotient and the square are IEEE fp64 operations without
+ *   contraction and llrint rounds half to even, so an fp64 restatement reproduces every integer.
+ *   thresholds: HOST array of T <= DMVS_DEPTH_MAX_THRESHOLDS floats (not NaN).
+ *   band_lo, band_hi: the `thres` band of AbsDepthError_metrics, 0 <= band_lo <= band_hi; (0, +inf) scores every valid pixel.
+ *   big: finite, > 0.   scale: a positive power of two with big * scale * max(HW, 1) < 2^62 (no item's sum can overflow);
+ *   scale_sq = scale / p, p the smallest power of two >= big, so that big^2 * scale_sq <= big * scale.
+ *   blocks: workgroups PER ITEM of the grid-stride launch, 0 = the library's choice (the result does not depend on it).
+ * Registers, wave shuffles, LDS, then one integer atomic per slot per workgroup: bitwise independent of launch order and grid shape.
+ * Pixels are read 16 bytes at a time where est, gt and mask share one 16-byte phase (always the case for whole torch allocations), with a
+ * scalar head and tail per item; otherwise one by one.  Same integers either way.
+ * DMVS_EINVAL (before any launch): NULL est / gt / out with B * HW > 0, pointers not 4-byte aligned, B or HW < 0, B > 65535, T outside
+ * [0, DMVS_DEPTH_MAX_THRESHOLDS], a NaN threshold, a band that is NaN / negative / empty, big or scale outside the above, blocks < 0. */
+#define DMVS_DEPTH_MAX_THRESHOLDS 8
+#define DMVS_DEPTH_SLOTS 7
+int dmvs_depth_stats_f32(const float* est, const float* gt, const float* mask, int64_t B, int64_t HW, const float* thresholds, int32_t T,
+                         double band_lo, double band_hi, double big, double scale, int32_t blocks, int64_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
