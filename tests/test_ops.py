@@ -1,6 +1,8 @@
 """Kernel-level parity: every C-ABI entry point against the oracle / the matching ATen op.
 Runs twice: on the host emulation of the kernel sources (CPU container) and, with -m gpu,
 through libdmvs_hip.so on the MI355X."""
+import collections
+import functools
 import os
 
 import numpy as np
@@ -1959,7 +1961,9 @@ def test_mask_upsample4(ops, B, H, W):
 def test_conv2d_wgrad_16_byte_staging_pieces(ops, cin, cout, k, stride, pad, H, W, two):
     """the weight-gradient kernel with both tiles staged in 16-byte LDS-DMA pieces (round 6: 9 instead of 27 DMA instructions per lane and
     tile) against autograd, and bit for bit against the 4-byte form (DMVS_TUNE_PIECES4): channel counts that are not multiples of the
-    8-channel workgroup slice, a concatenated second input, ragged tiles in y, stride 2, several tiles per workgroup"""
+    8-channel workgroup slice, a concatenated second input, ragged tiles in y, stride 2.  Every row has at most as many tiles as the grid
+    has workgroups (the largest: 18 tiles on 18), so each workgroup reduces ONE tile here; the grids on which workgroups walk several
+    tiles are test_conv2d_wgrad_walking_tiles_exact / _precision below"""
     B = 2
     ks = (k, k) if isinstance(k, int) else k
     pd = (pad, pad) if isinstance(pad, int) else pad
@@ -1986,3 +1990,289 @@ def test_conv2d_wgrad_16_byte_staging_pieces(ops, cin, cout, k, stride, pad, H, 
     close(run_w, 0.5 + 2 * w.grad, 4e-4)
     close(run_b, -1.0 + 2 * bias.grad, 4e-4)
     assert torch.equal(run_w.cpu(), (0.5 + gw.cpu()) + gw.cpu())
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# The weight-gradient kernels past one tile per workgroup.  conv2d_wgrad_kernel / conv3d_wgrad_kernel walk tiles
+# `tile = blockIdx.x; tile < ntiles; tile += gridDim.x` with ONE accumulator chain per wave, write one partial per workgroup, and a fold
+# kernel sums the gx partials (4 x 16-way unrolled loop + tail).  gx = min(ceil(1024 / (gy * gz)), ntiles): every other wgrad / autograd row
+# of this file has ntiles <= gx, so none of them runs the second iteration of the walk (the barrier guarding LDS reuse, re-staging over the
+# previous tile's halo, the batch crossing inside one walk, the uneven split) or the unrolled branch of the fold.  The rows below do, and
+# each ASSERTS the grid property it exists for: retuning the grid must fail them, not quietly put them back to one tile per workgroup.
+#   exact:     inputs and output gradients drawn from {-2..2}: every product and partial sum is an integer below 2^24 (B*Hout*Wout <= 2^21;
+#              the gated rows multiply three such values, |.| <= 8, over <= 2^15 pixels), so fp32 is exact in ANY summation order and the
+#              kernel must EQUAL the fp64 gradient -- a skipped, repeated or half-staged tile cannot hide in a tolerance.
+#   precision: uniform inputs; yardstick = ATen's own fp32 CPU gradient against the fp64 one, as close() measures (max abs error over
+#              max(1, |ref|.max())); the kernel's error may be 8 x that (one fp32 MFMA chain per wave over every tile it walks, then 4
+#              waves, then gx slots; ATen's blocked GEMM has shorter chains).
+
+
+def _ints(*shape, seed=0):
+    rs = np.random.RandomState(seed + sum(shape))
+    return torch.from_numpy(rs.randint(-2, 3, shape).astype(np.float32))
+
+
+def _wgrad_slots(ops, entry, desc, gy, gz, ntn):
+    """gx (workgroups walking the tiles = workspace slots per (cin chunk, cout tile)) from the library's own workspace size"""
+    import ctypes as C
+    nbytes = C.c_int64(0)
+    ops.lib.call(entry, C.byref(desc), C.byref(nbytes))
+    per = gy * gz * ntn * 256 * 4
+    assert nbytes.value > 0 and nbytes.value % per == 0, (nbytes.value, per)
+    return nbytes.value // per
+
+
+def _assert_walk(props, gx, ntiles):
+    """the grid properties a case exists for"""
+    assert props and set(props) <= {"single", "uneven", "several", "unrolled"}, props
+    if "single" in props:
+        assert ntiles == gx, f"one tile per workgroup wanted: {ntiles} tiles on {gx} workgroups"
+    if "uneven" in props:
+        assert gx < ntiles < 2 * gx, f"uneven walk wanted (some workgroups one tile more than others): {ntiles} tiles on {gx} workgroups"
+    if "several" in props:
+        assert ntiles >= 2 * gx, f"every workgroup walking at least two tiles wanted: {ntiles} tiles on {gx} workgroups"
+    if "unrolled" in props:
+        assert gx >= 49, f"the fold kernel's unrolled loop needs 49 slots: {gx}"
+
+
+def _rel_err(got, ref64):
+    return float((got.detach().cpu().double() - ref64).abs().max()) / max(1.0, float(ref64.abs().max()))
+
+
+def _assert_precision(what, dev_name, got, ref32, ref64, factor=8.0):
+    yard, err = _rel_err(ref32, ref64), _rel_err(got, ref64)
+    print(f"{what} on {dev_name}: ATen fp32 vs fp64 {yard:.3e}, kernel vs fp64 {err:.3e}, ratio {err / max(yard, 1e-30):.2f}")
+    assert torch.isfinite(got).all()
+    assert err <= factor * yard, f"{what}: kernel error {err:.3e} is {err / max(yard, 1e-30):.2f} x ATen's fp32 error {yard:.3e} (allowed {factor})"
+
+
+# c0 / c1: channels of x0 (as stored) / of the concatenated second input; H, W: x0's stored size (UPSAMPLE2: half, UNSHUFFLE2: twice the
+# convolution's input); gate: x0 = h is multiplied by r (`mul0`) as it is staged.  Widths: multiples of 4 where the row should take the
+# 16-byte form by default (its bit-for-bit comparison with DMVS_TUNE_PIECES4 then compares two kernels); `gated` has W = 102.
+# Grid and measured precision figures per row -- kernel error vs fp64 (the same on the emulation and on the MI355X: same products, same
+# order): then ATen's fp32 error vs fp64 = the yardstick, with (kernel error / yardstick; must be <= 8), first where the CPU suite ran,
+# second on the MI355X's host (ATen's blocking follows the host's thread count):
+#   case                    gx  tiles | gw kernel: yardstick (ratio) CPU suite, MI355X host | gb likewise
+#   k33s1                  114    147 | gw 2.5e-07: 1.1e-06 (0.22), 9.3e-07 (0.27) | gb 2.6e-07: 1.3e-06 (0.19), 9.5e-07 (0.27)
+#   k33s1_two_inputs       114    147 | gw 2.4e-07: 1.5e-06 (0.17), 9.0e-07 (0.27) | gb 2.6e-07: 1.3e-06 (0.19), 9.5e-07 (0.27)
+#   k11                     32    108 | gw 2.9e-07: 9.0e-07 (0.33), 8.3e-07 (0.36) | gb 2.0e-07: 2.2e-06 (0.09), 1.5e-06 (0.13)
+#   k33s2                   64     84 | gw 2.2e-07: 1.2e-06 (0.18), 1.2e-06 (0.18) | gb 2.6e-07: 1.6e-06 (0.16), 1.6e-06 (0.16)
+#   k55s2                   64     70 | gw 1.8e-07: 5.0e-06 (0.04), 5.0e-06 (0.04) | gb 2.2e-07: 7.0e-06 (0.03), 7.0e-06 (0.03)
+#   k77s1                   64     70 | gw 1.9e-07: 3.9e-06 (0.05), 3.9e-06 (0.05) | gb 2.2e-07: 7.0e-06 (0.03), 7.0e-06 (0.03)
+#   k15                     64     70 | gw 1.8e-07: 1.5e-06 (0.12), 1.1e-06 (0.17) | gb 1.3e-07: 9.7e-07 (0.13), 6.3e-07 (0.21)
+#   k51                     64     70 | gw 2.3e-07: 1.3e-06 (0.17), 9.6e-07 (0.24) | gb 1.5e-07: 8.7e-07 (0.18), 8.8e-07 (0.17)
+#   upsample2             1024   1058 | gw 1.9e-07: 7.7e-06 (0.02), 7.7e-06 (0.02) | gb 3.7e-08: 4.2e-06 (0.01), 4.2e-06 (0.01)
+#   unshuffle2             512    544 | gw 2.5e-07: 6.0e-07 (0.41), 6.9e-07 (0.36) | gb 1.2e-07: 3.8e-06 (0.03), 3.8e-06 (0.03)
+#   gated_one_tile           2      2 | gw 1.7e-07: 3.8e-07 (0.44), 3.8e-07 (0.44) | gb 1.3e-07: 2.3e-07 (0.57), 2.3e-07 (0.57)
+#   gated                  114    147 | gw 2.1e-07: 1.3e-06 (0.17), 7.5e-07 (0.28) | gb 1.9e-07: 1.3e-06 (0.14), 1.1e-06 (0.18)
+# On the emulation a walking launch costs about as much whatever the channels (gy * gz * tiles >= 1024 workgroup-tiles); k77s1 is the
+# dearest row (25 MFMA column tiles per pixel group).
+_W2 = collections.namedtuple("_W2", "name c0 c1 cout k stride pad mode gate B H W props")
+_WGRAD2D = [
+    _W2("k33s1", 24, 0, 40, (3, 3), 1, (1, 1), "plain", False, 3, 100, 104, ("uneven", "unrolled")),
+    _W2("k33s1_two_inputs", 19, 5, 40, (3, 3), 1, (1, 1), "plain", False, 3, 100, 104, ("uneven", "unrolled")),
+    _W2("k11", 64, 0, 64, (1, 1), 1, (0, 0), "plain", False, 3, 96, 96, ("several",)),
+    _W2("k33s2", 29, 0, 52, (3, 3), 2, (1, 1), "plain", False, 2, 165, 200, ("uneven", "unrolled")),
+    _W2("k55s2", 13, 0, 120, (5, 5), 2, (2, 2), "plain", False, 2, 140, 200, ("uneven", "unrolled")),
+    _W2("k77s1", 12, 0, 120, (7, 7), 1, (3, 3), "plain", False, 2, 70, 100, ("uneven", "unrolled")),
+    _W2("k15", 29, 0, 60, (1, 5), 1, (0, 2), "plain", False, 2, 70, 100, ("uneven", "unrolled")),
+    _W2("k51", 29, 0, 60, (5, 1), 1, (2, 0), "plain", False, 2, 66, 108, ("uneven", "unrolled")),
+    _W2("upsample2", 8, 0, 8, (3, 3), 1, (1, 1), "upsample", False, 2, 180, 184, ("uneven", "unrolled")),
+    _W2("unshuffle2", 4, 0, 12, (1, 1), 1, (0, 0), "unshuffle", False, 2, 520, 500, ("uneven", "unrolled")),
+    _W2("gated_one_tile", 12, 10, 16, (3, 3), 1, (1, 1), "plain", True, 2, 12, 16, ("single",)),
+    _W2("gated", 19, 5, 40, (3, 3), 1, (1, 1), "plain", True, 3, 100, 102, ("uneven", "unrolled")),
+]
+_IN_MODES = {"plain": K.IN_PLAIN, "upsample": K.IN_UPSAMPLE2, "unshuffle": K.IN_UNSHUFFLE2}
+
+
+def _wgrad2d_geometry(c):
+    """cin, (Hin, Win) of the convolution's input, (Hout, Wout)"""
+    if c.mode == "upsample":
+        cin, Hin, Win = c.c0 + c.c1, 2 * c.H, 2 * c.W
+    elif c.mode == "unshuffle":
+        cin, Hin, Win = 4 * c.c0 + c.c1, c.H // 2, c.W // 2
+    else:
+        cin, Hin, Win = c.c0 + c.c1, c.H, c.W
+    Hout = (Hin + 2 * c.pad[0] - c.k[0]) // c.stride + 1
+    Wout = (Win + 2 * c.pad[1] - c.k[1]) // c.stride + 1
+    return cin, (Hin, Win), (Hout, Wout)
+
+
+@functools.lru_cache(maxsize=None)
+def _wgrad2d_data(c, exact):
+    """inputs of a case and its reference gradients, computed once for both backends and left alone: ATen's autograd on the CPU through
+    F.conv2d(cat(r * h, x), w, b) in fp64 (and, for the precision rows, in fp32: the yardstick)"""
+    draw = _ints if exact else rnd
+    cin, _, (Hout, Wout) = _wgrad2d_geometry(c)
+    x0 = draw(c.B, c.c0, c.H, c.W, seed=1)
+    x1 = draw(c.B, c.c1, c.H, c.W, seed=2) if c.c1 else None
+    r = draw(c.B, c.c0, c.H, c.W, seed=3) if c.gate else None
+    g = draw(c.B, c.cout, Hout, Wout, seed=4)
+
+    def grads(dt):
+        a = x0.to(dt) * r.to(dt) if c.gate else x0.to(dt)
+        if c.mode == "upsample":
+            a = F.interpolate(a, scale_factor=2, mode="nearest")
+        elif c.mode == "unshuffle":
+            a = O._pixel_unshuffle(a)
+        if x1 is not None:
+            a = torch.cat([a, x1.to(dt)], 1)
+        w = torch.zeros(c.cout, cin, *c.k, dtype=dt, requires_grad=True)
+        b = torch.zeros(c.cout, dtype=dt, requires_grad=True)
+        F.conv2d(a, w, b, c.stride, c.pad).backward(g.to(dt))
+        return w.grad, b.grad
+    return dict(x0=x0, x1=x1, r=r, g=g, ref64=grads(torch.float64), ref32=None if exact else grads(torch.float32))
+
+
+def _wgrad2d_grid(ops, c):
+    """(gx, ntiles) of a case; gx from dmvs_conv2d_wgrad_workspace_f32"""
+    from diffmvs_amd import _lib
+    cin, (Hin, Win), (Hout, Wout) = _wgrad2d_geometry(c)
+    anchor = ops.empty(4)                                  # any non-null in0: the workspace query does not read it
+    desc = _lib.Conv2dDesc(in0=anchor.data_ptr(), in1=anchor.data_ptr() if c.c1 else None, B=c.B, c0=cin - c.c1, c1=c.c1, Hin=Hin, Win=Win,
+                           Hout=Hout, Wout=Wout, cout=c.cout, cout_pad=K._pad_cout(c.cout), kh=c.k[0], kw=c.k[1], stride=c.stride,
+                           pad_h=c.pad[0], pad_w=c.pad[1], in_mode=_IN_MODES[c.mode], out_cstride=c.cout, post_scale=1.0)
+    gy, gz, ntn = -(-cin // 8), -(-c.cout // 16), -(-(8 * c.k[0] * c.k[1] + 1) // 16)
+    gx = _wgrad_slots(ops, "dmvs_conv2d_wgrad_workspace_f32", desc, gy, gz, ntn)
+    return gx, -(-Wout // 16) * -(-Hout // 16) * c.B
+
+
+def _wgrad2d_call(ops, c, d):
+    cin = _wgrad2d_geometry(c)[0]
+    pc = K.pack_conv2d(torch.zeros(c.cout, cin, *c.k), None, stride=c.stride, pad=c.pad)      # the kernels read its geometry only
+    x0, g, x1, r = dev(ops, d["x0"], d["g"], d["x1"], d["r"])
+    return lambda **kw: ops.conv2d_wgrad(pc, x0, g, x1, mul0=r, in_mode=_IN_MODES[c.mode], want_bias=True, **kw)
+
+
+_WGRAD2D_IDS = [c.name for c in _WGRAD2D]
+
+
+@pytest.mark.parametrize("case", _WGRAD2D, ids=_WGRAD2D_IDS)
+def test_conv2d_wgrad_walking_tiles_exact(ops, case):
+    """every instantiation of conv2d_wgrad_kernel the training graph uses, on grids where workgroups walk (see the block comment above):
+    integer-valued inputs, so gw and gb EQUAL the fp64 gradient; the 16-byte form equals the 4-byte form (rows whose shape admits the
+    16-byte form: plain un-gated inputs, widths that are multiples of 4), two launches agree bit for bit, and the accumulate mode
+    started from an integer-valued running gradient gives run + 2 * gw exactly"""
+    gx, ntiles = _wgrad2d_grid(ops, case)
+    _assert_walk(case.props, gx, ntiles)
+    d = _wgrad2d_data(case, True)
+    want_w, want_b = (t.float() for t in d["ref64"])
+    assert float(d["ref64"][0].abs().max()) < 2 ** 24 and float(d["ref64"][1].abs().max()) < 2 ** 24
+    call = _wgrad2d_call(ops, case, d)
+    gw, gb = call()
+    assert torch.equal(gw.cpu(), want_w), f"gw differs from the fp64 gradient in {int((gw.cpu() != want_w).sum())} of {want_w.numel()} elements"
+    assert torch.equal(gb.cpu(), want_b), f"gb differs from the fp64 gradient in {int((gb.cpu() != want_b).sum())} of {want_b.numel()} elements"
+    gw4, gb4 = call(tune=K._lib.TUNE_PIECES4)
+    assert torch.equal(gw4, gw) and torch.equal(gb4, gb)
+    gw2, gb2 = call()
+    assert torch.equal(gw2, gw) and torch.equal(gb2, gb)
+    run_w, run_b = _ints(*want_w.shape, seed=5), _ints(*want_b.shape, seed=6)
+    acc_w, acc_b = dev(ops, run_w.clone(), run_b.clone())
+    for _ in range(2):
+        call(into_gw=acc_w, into_gb=acc_b)
+    assert torch.equal(acc_w.cpu(), run_w + 2 * want_w) and torch.equal(acc_b.cpu(), run_b + 2 * want_b)
+
+
+@pytest.mark.parametrize("case", _WGRAD2D, ids=_WGRAD2D_IDS)
+def test_conv2d_wgrad_walking_tiles_precision(ops, case):
+    """the same grids with uniform(-1, 1) inputs: the kernel's error against the fp64 gradient is at most 8 x the error of ATen's own
+    fp32 CPU gradient (both as close() measures them); the figures are printed before they are asserted"""
+    gx, ntiles = _wgrad2d_grid(ops, case)
+    _assert_walk(case.props, gx, ntiles)
+    d = _wgrad2d_data(case, False)
+    gw, gb = _wgrad2d_call(ops, case, d)()
+    _assert_precision(f"conv2d wgrad {case.name} gw", ops.device, gw, d["ref32"][0], d["ref64"][0])
+    _assert_precision(f"conv2d wgrad {case.name} gb", ops.device, gb, d["ref32"][1], d["ref64"][1])
+
+
+# cin / cout / D, H, W: of the KERNEL's input x and output gradient g (for the transposed layer's weight gradient those are the layer's
+# output gradient and input: roles swapped, as _Conv3dFn.backward calls it).  Tiles are 16 x 4 x 4 output voxels.
+#   case                    gx  tiles | gw kernel: yardstick (ratio) CPU suite, MI355X host | gb likewise (rows that ask for it)
+#   s1_ragged_chunk        256    288 | gw 1.7e-07: 3.7e-07 (0.47), 3.7e-07 (0.47) | gb 2.1e-07: 9.9e-07 (0.21), 9.9e-07 (0.21)
+#   s1                     128    150 | gw 2.4e-07: 3.7e-06 (0.07), 2.4e-06 (0.10)
+#   s1_several_tiles        32     64 | gw 2.3e-07: 2.6e-06 (0.09), 2.6e-06 (0.09) | gb 1.4e-07: 9.7e-07 (0.15), 9.7e-07 (0.15)
+#   s2                      64     72 | gw 2.0e-07: 1.6e-06 (0.12), 1.0e-06 (0.20)
+#   s2_transposed_layer     64     72 | gw 2.0e-07: 1.7e-06 (0.11), 1.3e-06 (0.16)
+_W3 = collections.namedtuple("_W3", "name cin cout stride B D H W bias transposed props")
+_WGRAD3D = [
+    _W3("s1_ragged_chunk", 12, 24, 1, 2, 14, 22, 88, True, False, ("uneven", "unrolled")),
+    _W3("s1", 32, 32, 1, 2, 12, 20, 80, False, False, ("uneven", "unrolled")),
+    _W3("s1_several_tiles", 60, 56, 1, 2, 7, 14, 62, True, False, ("several",)),
+    _W3("s2", 16, 32, 2, 3, 16, 32, 96, False, False, ("uneven", "unrolled")),
+    _W3("s2_transposed_layer", 16, 32, 2, 3, 16, 32, 96, False, True, ("uneven", "unrolled")),
+]
+_WGRAD3D_IDS = [c.name for c in _WGRAD3D]
+
+
+def _wgrad3d_out(c):
+    return tuple((n - 1) // c.stride + 1 for n in (c.D, c.H, c.W))
+
+
+@functools.lru_cache(maxsize=None)
+def _wgrad3d_data(c, exact):
+    """inputs and CPU reference gradients (fp64; fp32 for the precision rows), computed once: autograd through F.conv3d, or -- the
+    transposed layer -- through F.conv_transpose3d(g, w) with x as ITS output gradient"""
+    draw = _ints if exact else rnd
+    x = draw(c.B, c.cin, c.D, c.H, c.W, seed=7 if c.transposed else 1)
+    g = draw(c.B, c.cout, *_wgrad3d_out(c), seed=8 if c.transposed else 2)
+
+    def grads(dt):
+        w = torch.zeros(c.cout, c.cin, 3, 3, 3, dtype=dt, requires_grad=True)
+        if c.transposed:
+            F.conv_transpose3d(g.to(dt), w, None, 2, 1, 1).backward(x.to(dt))
+            return w.grad, None
+        b = torch.zeros(c.cout, dtype=dt, requires_grad=True)
+        F.conv3d(x.to(dt), w, b, c.stride, 1).backward(g.to(dt))
+        return w.grad, b.grad
+    return dict(x=x, g=g, ref64=grads(torch.float64), ref32=None if exact else grads(torch.float32))
+
+
+def _wgrad3d_grid(ops, c):
+    """(gx, ntiles) of a case; gx from dmvs_conv3d_wgrad_workspace_f32"""
+    from diffmvs_amd import _lib
+    Do, Ho, Wo = _wgrad3d_out(c)
+    anchor = ops.empty(4)
+    desc = _lib.Conv3dDesc(in_=anchor.data_ptr(), B=c.B, cin=c.cin, cout=c.cout, cout_pad=K._pad_cout(c.cout), Din=c.D, Hin=c.H, Win=c.W,
+                           Dout=Do, Hout=Ho, Wout=Wo, stride=c.stride, transposed=0)
+    ck = 8 if c.stride == 1 else 2
+    gx = _wgrad_slots(ops, "dmvs_conv3d_wgrad_workspace_f32", desc, -(-c.cin // ck), -(-c.cout // 16), -(-(ck * 27 + 1) // 16))
+    return gx, -(-Wo // 16) * -(-Ho // 4) * -(-Do // 4) * c.B
+
+
+def _wgrad3d_call(ops, c, d):
+    x, g = dev(ops, d["x"], d["g"])
+
+    def call():
+        out = ops.conv3d_wgrad(x, g, cout=c.cout, stride=c.stride, want_bias=c.bias)
+        return out if c.bias else (out, None)
+    return call
+
+
+@pytest.mark.parametrize("case", _WGRAD3D, ids=_WGRAD3D_IDS)
+def test_conv3d_wgrad_walking_tiles_exact(ops, case):
+    """conv3d_wgrad_kernel<1> / <2> on grids where workgroups walk: integer-valued inputs, gw (and gb) EQUAL the fp64 gradient, and two
+    launches agree bit for bit"""
+    gx, ntiles = _wgrad3d_grid(ops, case)
+    _assert_walk(case.props, gx, ntiles)
+    d = _wgrad3d_data(case, True)
+    want_w, want_b = (None if t is None else t.float() for t in d["ref64"])
+    assert float(d["ref64"][0].abs().max()) < 2 ** 24
+    call = _wgrad3d_call(ops, case, d)
+    gw, gb = call()
+    assert torch.equal(gw.cpu(), want_w), f"gw differs from the fp64 gradient in {int((gw.cpu() != want_w).sum())} of {want_w.numel()} elements"
+    if case.bias:
+        assert torch.equal(gb.cpu(), want_b), f"gb differs from the fp64 gradient in {int((gb.cpu() != want_b).sum())} of {want_b.numel()} elements"
+    gw2, gb2 = call()
+    assert torch.equal(gw2, gw) and (not case.bias or torch.equal(gb2, gb))
+
+
+@pytest.mark.parametrize("case", _WGRAD3D, ids=_WGRAD3D_IDS)
+def test_conv3d_wgrad_walking_tiles_precision(ops, case):
+    """the same grids with uniform(-1, 1) inputs: error against fp64 at most 8 x that of ATen's own fp32 CPU gradient"""
+    gx, ntiles = _wgrad3d_grid(ops, case)
+    _assert_walk(case.props, gx, ntiles)
+    d = _wgrad3d_data(case, False)
+    gw, gb = _wgrad3d_call(ops, case, d)()
+    _assert_precision(f"conv3d wgrad {case.name} gw", ops.device, gw, d["ref32"][0], d["ref64"][0])
+    if case.bias:
+        _assert_precision(f"conv3d wgrad {case.name} gb", ops.device, gb, d["ref32"][1], d["ref64"][1])
