@@ -207,6 +207,26 @@ __device__ __forceinline__ void cloud_block_sum(CloudSums<N> acc, int live, unsi
     }
 }
 
+// The integer minimum of the z-buffer splat (cloud_render.hip): one no-return u32 atomic-min on the device; under the host emulation, whose
+// header has integer atomicAdd only, a compare-exchange loop on the compiler builtin.  dmvs_peek_u32 is the plain load in front of it (the
+// value may be stale; the caller only ever uses it as an upper bound of a value that never rises).
+__device__ __forceinline__ void dmvs_atomic_min_u32(unsigned* p, unsigned v) {
+#ifdef DMVS_HOST_EMULATION
+    unsigned old = __atomic_load_n(p, __ATOMIC_RELAXED);
+    while (v < old && !__atomic_compare_exchange_n(p, &old, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {
+    }
+#else
+    atomicMin(p, v);
+#endif
+}
+__device__ __forceinline__ unsigned dmvs_peek_u32(const unsigned* p) {
+#ifdef DMVS_HOST_EMULATION
+    return __atomic_load_n(p, __ATOMIC_RELAXED);
+#else
+    return *p;
+#endif
+}
+
 // host side of such a launch: the scale is a positive finite power of two ...
 inline bool cloud_pow2(double s) {
     int e = 0;

@@ -886,3 +886,47 @@ class Ops:
         self._call("dmvs_depth_stats_f32", _ptr(est), _ptr(gt), _ptr(mask), B, HW, thr, T, lo, hi, float(big), float(scale), int(blocks),
                    _ptr(out), self.stream())
         return out
+
+    # ------------------------------------------------------------------ depth maps from a cloud (diffmvs_amd/cloud_render.py)
+    def _splat_args(self, what, points, views, size, zbuf):
+        """the checks both splat passes share -> (N, V, H, W, the HOST view table)"""
+        import numpy as np
+        self._chk_typed(what, (points, torch.float32), (zbuf, torch.float32))
+        if points.dim() != 2 or points.shape[1] != 3:
+            raise _lib.DmvsError(f"{what}: points must be [N,3], got {tuple(points.shape)}")
+        v = np.ascontiguousarray(views.detach().cpu().numpy() if torch.is_tensor(views) else views, dtype=np.float64)
+        if v.ndim != 2 or v.shape[1] != _lib.SPLAT_VIEW_DOUBLES:
+            raise _lib.DmvsError(f"{what}: views must be [V,{_lib.SPLAT_VIEW_DOUBLES}] (two rows of P, row 2 of E, f, near, far), got {v.shape}")
+        H, W = int(size[0]), int(size[1])
+        V = int(v.shape[0])
+        if zbuf is not None and tuple(zbuf.shape) != (V, H, W):
+            raise _lib.DmvsError(f"{what}: the z-buffer must be [V,H,W] = {(V, H, W)}, got {tuple(zbuf.shape)}")
+        return int(points.shape[0]), V, H, W, v
+
+    def cloud_splat_zmin(self, points, views, size, radius, r_min, r_max, zbuf=None, transform=None, pretest=True, work=False, blocks=0):
+        """dmvs_cloud_splat_zmin_f32 (include/dmvs.h): the nearest depth per pixel of every point's footprint.  points [N,3] fp32; views
+        [V,15] fp64 on the host (cloud_render.view_table); size (H, W); zbuf: None (a fresh [V,H,W] fp32 buffer of +inf) or one to go on with.
+        -> (zbuf, counts [V,4] int64: non-finite, outside the depth range, off the image, radius clamped[, work [2] int64: footprint
+        pixels visited, atomics issued])"""
+        N, V, H, W, v = self._splat_args("cloud_splat_zmin", points, views, size, zbuf)
+        if zbuf is None:
+            zbuf = torch.full((V, H, W), float("inf"), dtype=torch.float32, device=self.device)
+        fresh = torch.empty if N > 0 and V > 0 else torch.zeros      # (the library zeroes both, unless there is nothing to do)
+        counts = fresh((V, _lib.SPLAT_SLOTS), dtype=torch.int64, device=self.device)
+        wk = fresh((2,), dtype=torch.int64, device=self.device) if work else None
+        self._call("dmvs_cloud_splat_zmin_f32", _ptr(points), N, self._transform_arg(transform), v.ctypes.data_as(C.c_void_p), V, H, W, float(radius),
+                   float(r_min), float(r_max), 0 if pretest else _lib.SPLAT_NO_PRETEST, int(blocks), _ptr(zbuf), _ptr(counts), _ptr(wk), self.stream())
+        return (zbuf, counts, wk) if work else (zbuf, counts)
+
+    def cloud_splat_sum(self, points, views, size, radius, r_min, r_max, zbuf, tau, scale, transform=None, blocks=0):
+        """dmvs_cloud_splat_sum_f32 (include/dmvs.h): over the finished z-buffer of cloud_splat_zmin (same points, views and radii), the
+        fixed-point sum and the count of the depths within (1 + tau) of each pixel's nearest.  -> (sum [V,H,W] int64, cnt [V,H,W] int32)"""
+        N, V, H, W, v = self._splat_args("cloud_splat_sum", points, views, size, zbuf)
+        if zbuf is None:
+            raise _lib.DmvsError("cloud_splat_sum: needs the z-buffer of cloud_splat_zmin")
+        fresh = torch.empty if N > 0 and V > 0 and H * W > 0 else torch.zeros      # (the library zeroes both, unless there is nothing to do)
+        total = fresh((V, H, W), dtype=torch.int64, device=self.device)
+        cnt = fresh((V, H, W), dtype=torch.int32, device=self.device)
+        self._call("dmvs_cloud_splat_sum_f32", _ptr(points), N, self._transform_arg(transform), v.ctypes.data_as(C.c_void_p), V, H, W, float(radius),
+                   float(r_min), float(r_max), float(tau), float(scale), int(blocks), _ptr(zbuf), _ptr(total), _ptr(cnt), self.stream())
+        return total, cnt

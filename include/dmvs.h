@@ -604,6 +604,48 @@ int dmvs_cloud_crop_prism_f32(const float* points, int64_t N, const double* tran
 int dmvs_depth_stats_f32(const float* est, const float* gt, const float* mask, int64_t B, int64_t HW, const float* thresholds, int32_t T,
                          double band_lo, double band_hi, double big, double scale, int32_t blocks, int64_t* out, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Ground-truth depth maps from a cloud (added under ABI 4, additive; diffmvs_amd/cloud_render.py): a scatter with a z-buffer, two passes
+ * over the same walk.
+ *
+ * points [N,3] fp32 (device).  transform: as above (HOST 3x4 or NULL), applied first; the moved point is fp32.
+ * views: HOST [V, DMVS_SPLAT_VIEW_DOUBLES] doubles per view: rows 0 and 1 of P = K E[:3] (4 + 4), row 2 of E (4), f = K[0][0], near, far.
+ * Per (point (X, Y, Z) widened to fp64, view), IEEE fp64 in exactly this order, no contraction:
+ *     x = ((P00 X + P01 Y) + P02 Z) + P03      y likewise with row 1      z = ((E20 X + E21 Y) + E22 Z) + E23
+ *     slot 0 and no more if X, Y or Z is not finite;  slot 1 unless near < z <= far
+ *     u = x / z, v = y / z (pixel centres at integer coordinates);  slot 2 if u or v is not finite
+ *     r = fmin(fmax(radius * f / z, r_min), r_max)
+ *     columns fmax(ceil(u - r), 0) .. fmin(floor(u + r), W - 1), rows likewise with v and H, clamped in fp64 and then converted;
+ *     slot 2 ("off the image") if either range is empty;  otherwise slot 3 if radius * f / z > r_max (the radius was clamped), and
+ *     z32 = (float)z goes to every pixel of the footprint:
+ * dmvs_cloud_splat_zmin_f32: zbuf[view][row][col] = min(zbuf, z32).  zbuf [V,H,W] fp32 is the CALLER's, pre-filled with +inf.  One u32
+ *   integer atomic-min on the bit pattern per pixel (z32 >= 0: the bits order like the values), behind a plain load that skips it when z32
+ *   cannot lower the pixel (flags & DMVS_SPLAT_NO_PRETEST: always issue it; same result).
+ *   counts [V, DMVS_SPLAT_SLOTS] int64 (device, zeroed here): the slots above, per view.
+ *   work: NULL or [2] uint64 (device, zeroed here): footprint pixels visited, atomics issued (the second depends on timing with the pre-test).
+ * dmvs_cloud_splat_sum_f32: the same walk over the FINISHED zbuf; for every footprint pixel with (double)z32 <= (double)zbuf * (1.0 + tau):
+ *   sum[pixel] += llrint((double)z32 * scale) (uint64) and cnt[pixel] += 1 (int32); sum, cnt [V,H,W] (device, zeroed here).
+ *   scale: a positive power of two with max(far) * scale * max(N, 1) < 2^62.
+ *   The mean depth of a pixel is (float)(((double)sum / (double)cnt) / scale) where cnt > 0, the nearest one zbuf where it is finite.
+ * blocks: workgroups of the grid-stride launch, 0 = the library's choice.  Views go DMVS_SPLAT_VIEW_CHUNK per launch as kernel arguments.
+ * Integer min and integer adds only: every output is bitwise independent of blocks, of the launch order and of the order of the points.
+ * N = 0 or V = 0: nothing is touched.  DMVS_EINVAL (before any launch): N, V, H, W or blocks < 0, N >= 2^31 (cnt and the slot counters of a workgroup are 32 bits), H W >= 2^31
+ * or V H W > 2^40, NULL operands with work to do, points / zbuf / cnt not 4-byte or counts / work / sum not 8-byte aligned, a view with a
+ * non-finite matrix entry, f < 0 or not finite, near <= 0, far <= near or far > FLT_MAX (NaN included), radius or r_min negative or not
+ * finite, r_max < r_min or r_max > DMVS_SPLAT_MAX_RADIUS (a footprint is at most 33 x 33 pixels), a non-finite transform, unknown flags,
+ * tau negative or not finite, a scale that is not a power of two or beyond the bound. */
+#define DMVS_SPLAT_VIEW_CHUNK 8
+#define DMVS_SPLAT_VIEW_DOUBLES 15
+#define DMVS_SPLAT_SLOTS 4
+#define DMVS_SPLAT_MAX_RADIUS 16
+#define DMVS_SPLAT_NO_PRETEST 0x1
+int dmvs_cloud_splat_zmin_f32(const float* points, int64_t N, const double* transform, const double* views, int64_t V, int32_t H, int32_t W,
+                              double radius, double r_min, double r_max, int32_t flags, int32_t blocks, float* zbuf, int64_t* counts,
+                              uint64_t* work, void* stream);
+int dmvs_cloud_splat_sum_f32(const float* points, int64_t N, const double* transform, const double* views, int64_t V, int32_t H, int32_t W,
+                             double radius, double r_min, double r_max, double tau, double scale, int32_t blocks, const float* zbuf,
+                             uint64_t* sum, int32_t* cnt, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
