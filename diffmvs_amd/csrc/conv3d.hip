@@ -1,16 +1,26 @@
 // fp32 3-D convolutions of PixelViewWeight / CostRegNet_small (reference
 // models/module.py:422-463): 3x3x3, padding 1.
 //
-// Stride-1 layers (all the large volumes) run as an implicit GEMM on the matrix cores,
-// the 3-D sibling of conv2d.hip:  workgroup = 16(x) x 4(y) x 4(d) output voxels x NT*16
-// channels, wave w = depth slice w (4 pixel-tiles of 16 consecutive x), K loop over chunks of
-// input channels staged in LDS as a [CK][6][6][18] halo tile + [CK][27][NT*16] weights,
-// v_mfma_f32_16x16x4_f32 with A = weights, B = voxels.
+// Every layer except the cout = 1 heads runs as an implicit GEMM on the matrix cores, the 3-D sibling of conv2d.hip
+// (conv3d_mfma_kernel):  workgroup = 16(x) x 4(y) x 4(d) output voxels x NT*16 channels, wave w = depth
+// slice w (4 pixel-tiles of 16 consecutive x), K loop over chunks of input channels staged in LDS by
+// LDS-DMA as a halo tile + [CK][27][NT*16] weights, v_mfma_f32_16x16x4_f32 with A = voxels, B = weights.
+// The stride-2 layers walk a 33 x 9 x 9 halo with stride 2 in the same kernel.  On top of it:
+//   conv3d_mfma_stream_kernel       cin <= 4: resident workgroups, the next tile's halo streams in under the MFMAs
+//   conv3d_mfma_stream_pair_kernel  cin <= 4 and cout <= 8: the same, two output depth slices share the 16 MFMA rows
+//   conv3d_mfma_stream_pair8_kernel 5..8 input channels: the paired kernel over two 4-channel chunks per tile
+//   conv3d_c1_kernel / _rows_kernel cout == 1: direct VALU form (an MFMA N-tile would be 94 % padding)
+//   deconv3d_mfma_kernel            the transposed layers in gather form, the two x-parities in one MFMA
+// Shared pieces come first: the halo maps and the tile walk (every kernel but c1_rows), stage_chunk (the per-tile staging of the three
+// resident kernels; the generic and transposed kernels form bounds and origin once per workgroup), TileEpi (stream and generic), and
+// the paired-weight rule and register tap nest of the two paired kernels.  The 27-tap nest of stream / generic and the paired epilogue
+// stay written out per kernel: as shared functions they changed the generated code and measured 0.3-1.5 % slower.
 //
-// The stride-2 and transposed layers act on 1/8 .. 1/64 of the volume and use the direct
-// form: one lane = one output voxel (x fastest), CO accumulators in VGPRs, tap weights
-// wave-uniform.  The transposed convolution is evaluated in gather form, one output parity
-// class (od&1, oh&1, ow&1) per blockIdx.z so that the live taps stay wave-uniform:
+// conv3d_kernel<CO,2> and deconv3d_kernel<CO> are the direct form: one lane = one output voxel
+// (x fastest), CO accumulators in VGPRs, tap weights wave-uniform.  They remain the only path for
+// cout_pad > 32 at stride 2 and for items of 2^31 elements or more.  The transposed convolution
+// is evaluated in gather form, one output parity class (od&1, oh&1, ow&1) per blockIdx.z so that
+// the live taps stay wave-uniform:
 //   o = 2j   : k = 1 reads i = j            o = 2j+1 : k = 0 reads i = j+1, k = 2 reads i = j
 
 #include <type_traits>
@@ -41,7 +51,7 @@ constexpr int pad16mod32_3d(int n) {
 __device__ __attribute__((aligned(16))) const float dmvs_zero16_3d[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 #define DMVS_LDS(p) ((__attribute__((address_space(3))) void*)(p))
 
-// ---- staging and epilogue pieces shared by the three stride-1 kernels ---------------------------------------------
+// ---- staging and epilogue pieces shared by the matrix-core kernels -------------------------------------------------
 // Halo tiles go HBM/L2 -> LDS by LDS-DMA, 4 bytes per lane (their rows are not 16-byte multiples).  Which (z, y, x) of
 // a channel plane of the halo tile a lane's elements are never changes, so it is decoded ONCE per workgroup; per tile
 // only the border test remains, done for all three coordinates at once on the packed form:  with a guard bit above
@@ -50,8 +60,9 @@ __device__ __attribute__((aligned(16))) const float dmvs_zero16_3d[4] = {0.0f, 0
 // ~90 instructions per staged element: 560 VALU + 590 SALU per 108 MFMAs, SQ PMC on the 4->8 layer.)
 constexpr unsigned kHaloGuard = 0x00808080u;
 
-template <int ID, int IH, int IW, int PLANE>
+template <int ID, int IH, int IW, int PLANE_>
 struct HaloMap {
+    static constexpr int PLANE = PLANE_;
     static constexpr int P_IT = (PLANE + DMVS_BLOCK - 1) / DMVS_BLOCK;
     int off[P_IT];       // (zz * Hin + yy) * Win + xx, relative to the tile's halo origin
     int zyx[P_IT];       // zz | yy << 8 | xx << 16, or -1: not an element of the plane (row padding / beyond it)
@@ -148,6 +159,18 @@ struct HaloSel<true, ID, IH, IW> {
     static constexpr int PLANE = type::PLANE, PITCH = type::IWL, X0 = type::SLACK;
 };
 
+// CK channel planes of batch item b, from channel c0 on, of the halo tile at origin (gd0, gy0, gx0) -> buf[CK][PLANE]
+template <int CK, class Halo>
+__device__ __forceinline__ void stage_chunk(const Halo& halo, const dmvs_conv3d_desc& d, int b, int c0, int gd0, int gy0, int gx0, float* buf,
+                                            int wave) {
+    const int vol = d.Din * d.Hin * d.Win;
+    unsigned lo, him1;
+    Halo::bounds(gd0, gy0, gx0, d.Din, d.Hin, d.Win, lo, him1);
+    const float* origin = d.in + (size_t)b * d.cin * vol + ((long)gd0 * d.Hin + gy0) * d.Win + gx0;
+#pragma unroll
+    for (int ci = 0; ci < CK; ++ci) halo.stage(origin + (long)(c0 + ci) * vol, c0 + ci < d.cin, lo, him1, buf + ci * Halo::PLANE, wave);
+}
+
 // 16-byte halo pieces (HaloMap16) wherever rows are 16-byte multiples on a 16-byte aligned tensor: measured on the MI355X against the
 // 4-byte form, bit-identical (profiles/r4_optins_ab.jsonl): PixelViewWeight conv0 at 480 volumes 3318 -> 3231 us, CostRegNet conv0
 // 659 -> 646, conv1 1540 -> 1453, conv3 443 -> 415, conv5 268 -> 257.  DMVS_TUNE3D_PIECES4 forces the 4-byte form (A/B runs, tests).
@@ -241,6 +264,42 @@ struct TileEpi {
     }
 };
 
+// the tile walk of the MFMA and cout = 1 kernels: x fastest, after the XCD regrouping
+struct TilePos {
+    int b, td, ty, tx;
+};
+__device__ __forceinline__ TilePos conv3d_tile_pos(int tile, int ntiles, int tiles_x, int tiles_y, int tiles_d, int tune) {
+    tile = conv3d_xcd_tile(tile, ntiles, tune);
+    TilePos p;
+    p.tx = tile % tiles_x; tile /= tiles_x;
+    p.ty = tile % tiles_y; tile /= tiles_y;
+    p.td = tile % tiles_d;
+    p.b = tile / tiles_d;
+    return p;
+}
+
+// paired weights of (input channel ci, position jt = (j, ky, kx), MFMA row): rows 0-7 take W[kd = j], rows 8-15 W[kd = j - 1], zero outside
+__device__ __forceinline__ float paired_weight(const dmvs_conv3d_desc& d, int ci, int jt, int row) {
+    const int j = jt / 9, t9 = jt - j * 9;
+    const int kd = row < 8 ? j : j - 1, co = row & 7;
+    return (ci < d.cin && kd >= 0 && kd <= 2 && co < d.cout) ? d.weight[(ci * 27 + kd * 9 + t9) * d.cout_pad + co] : 0.0f;
+}
+
+// one 4-channel chunk of the paired kernel: 4 input slices x 9 taps against the lane's 36 paired weights (fully unrolled: register-resident
+// weights are indexed by compile-time constants); ipb = this lane's voxel in halo slice 2w = input slice (2w - 1)
+template <int IH, int IWP>
+__device__ __forceinline__ void conv3d_pair_taps(const float* ipb, const float (&w)[36], f32x4 (&acc)[4]) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+            for (int kx = 0; kx < 3; ++kx)
+#pragma unroll
+                for (int mt = 0; mt < 4; ++mt)      // D[voxel][(slice, cout)]
+                    acc[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(ipb[(j * IH + ky + mt) * IWP + kx], w[(j * 3 + ky) * 3 + kx], acc[mt], 0, 0, 0);
+}
+
 // resident workgroups per CU of the streamed kernel (28 KB LDS, 80 VGPRs each).  3 / 4 / 5 / 6 measured 898 / 881 / 880 / 891 us
 // on the 80-volume 4->8 layer: the kernel is not occupancy-limited.
 constexpr int kStreamWgsPerCu = 5;
@@ -269,7 +328,7 @@ __global__ void __launch_bounds__(DMVS_BLOCK) conv3d_mfma_stream_kernel(const dm
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // scalar: LDS-DMA bases stay in SGPRs
     const int m = lane & 15, kq = lane >> 4;
     const int nbase = blockIdx.y * NW;
-    const int vol = d.Din * d.Hin * d.Win, ovol = d.Dout * d.Hout * d.Wout;
+    const int ovol = d.Dout * d.Hout * d.Wout;
     const int ntiles = tiles_x * tiles_y * tiles_d * d.B;
 
     Halo halo;
@@ -282,43 +341,27 @@ __global__ void __launch_bounds__(DMVS_BLOCK) conv3d_mfma_stream_kernel(const dm
         slab.stage(d.weight, 0, d.cin, d.cout_pad, s_w, wave);
     }
 
-    auto stage = [&](int b, int td, int ty, int tx, float* buf) {
-        const int gx0 = tx * TX - 1, gy0 = ty * TY - 1, gd0 = td * TD - 1;
-        unsigned lo, him1;
-        Halo::bounds(gd0, gy0, gx0, d.Din, d.Hin, d.Win, lo, him1);
-        const float* origin = d.in + (size_t)b * d.cin * vol + ((long)gd0 * d.Hin + gy0) * d.Win + gx0;
-#pragma unroll
-        for (int ci = 0; ci < CK; ++ci) halo.stage(origin + (long)ci * vol, ci < d.cin, lo, him1, buf + ci * PLANE, wave);
-    };
-    auto decode = [&](int tile, int& b, int& td, int& ty, int& tx) {
-        tile = conv3d_xcd_tile(tile, ntiles, d.tune);
-        tx = tile % tiles_x; tile /= tiles_x;
-        ty = tile % tiles_y; tile /= tiles_y;
-        td = tile % tiles_d;
-        b = tile / tiles_d;
-    };
-
-    auto store = [&](const f32x4 (&a)[4][NT], int sb, int std_, int sty, int stx) {
-        const size_t ob = (size_t)sb * d.cout * ovol;
-        epi.store(d, a, d.out + ob, d.residual ? d.residual + ob : nullptr, stx * TX + 4 * kq, std_ * TD + wave, sty * TY, ovol);
+    auto store = [&](const f32x4 (&a)[4][NT], const TilePos& p) {
+        const size_t ob = (size_t)p.b * d.cout * ovol;
+        epi.store(d, a, d.out + ob, d.residual ? d.residual + ob : nullptr, p.tx * TX + 4 * kq, p.td * TD + wave, p.ty * TY, ovol);
     };
 
     int tile = blockIdx.x, cur = 0;
-    int b = 0, td = 0, ty = 0, tx = 0;
+    TilePos t = {0, 0, 0, 0}, prev = {-1, 0, 0, 0};
     f32x4 pend[4][NT];                  // the previous tile's accumulators: stored one iteration late, after the barrier, so
-    int pb = -1, ptd = 0, pty = 0, ptx = 0;     // that the barrier's vmcnt(0) (needed for the LDS-DMA) does not wait out fresh stores
+                                        // that the barrier's vmcnt(0) (needed for the LDS-DMA) does not wait out fresh stores
     if (tile < ntiles) {
-        decode(tile, b, td, ty, tx);
-        stage(b, td, ty, tx, lds);
+        t = conv3d_tile_pos(tile, ntiles, tiles_x, tiles_y, tiles_d, d.tune);
+        stage_chunk<CK>(halo, d, t.b, 0, t.td * TD - 1, t.ty * TY - 1, t.tx * TX - 1, lds, wave);
     }
     for (; tile < ntiles; tile += gridDim.x, cur ^= 1) {
         DMVS_DMA_BARRIER();            // this tile's halo (and, first time, the weights) landed; the other buffer is free
-        int nb = 0, ntd = 0, nty = 0, ntx = 0;
+        TilePos next = {0, 0, 0, 0};
         if (tile + (int)gridDim.x < ntiles) {
-            decode(tile + gridDim.x, nb, ntd, nty, ntx);
-            stage(nb, ntd, nty, ntx, lds + (cur ^ 1) * (CK * PLANE));
+            next = conv3d_tile_pos(tile + gridDim.x, ntiles, tiles_x, tiles_y, tiles_d, d.tune);
+            stage_chunk<CK>(halo, d, next.b, 0, next.td * TD - 1, next.ty * TY - 1, next.tx * TX - 1, lds + (cur ^ 1) * (CK * PLANE), wave);
         }
-        if (pb >= 0) store(pend, pb, ptd, pty, ptx);
+        if (prev.b >= 0) store(pend, prev);
         const float* s_in = lds + cur * (CK * PLANE);
         f32x4 acc[4][NT];
 #pragma unroll
@@ -326,9 +369,8 @@ __global__ void __launch_bounds__(DMVS_BLOCK) conv3d_mfma_stream_kernel(const dm
 #pragma unroll
             for (int j = 0; j < NT; ++j) acc[i][j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
         {
-            const int ci = kq;
-            const float* wp = s_w + ci * WPAD + m;
-            const float* ipb = s_in + ci * PLANE + wave * (IH * IWP) + HS::X0 + m;
+            const float* wp = s_w + kq * WPAD + m;                                 // k = input channel kq
+            const float* ipb = s_in + kq * PLANE + wave * (IH * IWP) + HS::X0 + m;
 #pragma unroll 1
             for (int kd = 0; kd < 3; ++kd) {
 #pragma unroll
@@ -353,93 +395,61 @@ __global__ void __launch_bounds__(DMVS_BLOCK) conv3d_mfma_stream_kernel(const dm
         for (int i = 0; i < 4; ++i)
 #pragma unroll
             for (int j = 0; j < NT; ++j) pend[i][j] = acc[i][j];
-        pb = b; ptd = td; pty = ty; ptx = tx;
-        b = nb; td = ntd; ty = nty; tx = ntx;
+        prev = t;
+        t = next;
     }
-    if (pb >= 0) store(pend, pb, ptd, pty, ptx);
+    if (prev.b >= 0) store(pend, prev);
 }
 
-// cin <= 4 AND cout <= 8 (PixelViewWeight conv0, CostReg conv0: 4 -> 8 on the largest volumes of the model): with 8 output
-// channels half of the 16 A rows of v_mfma_f32_16x16x4_f32 would be zero padding.  This variant gives the spare rows to a
+// cin <= 8 AND cout <= 8 (PixelViewWeight conv0, CostRegNet conv0: 4 -> 8 on the largest volumes of the model; CostRegNet conv1: 8 -> 8): with
+// 8 output channels half of the 16 weight rows of v_mfma_f32_16x16x4_f32 would be zero padding.  This variant gives the spare rows to a
 // SECOND OUTPUT DEPTH SLICE: a wave owns output slices 2w and 2w+1 of a 16(x) x 4(y) x 8(d) tile, and for input slice
-// j = -1 .. 2 (relative to 2w) and tap (ky, kx) the A operand is  rows 0-7 = W[kd = j+1] (output 2w), rows 8-15 = W[kd = j]
-// (output 2w+1), zero where kd falls outside 0..2 -- both outputs read the same B operand (the input slice).  4 x 9 x 4 = 144
-// MFMAs per wave produce two slices instead of 2 x 108: 1.5x fewer MFMAs for the same result, bit-identical per output
-// (each output still sums its 27 x cin products in (kd, ky, kx) order).  Same resident, tile-pipelined structure as
+// j = -1 .. 2 (relative to 2w) and tap (ky, kx) the weight operand is  rows 0-7 = W[kd = j+1] (output 2w), rows 8-15 = W[kd = j]
+// (output 2w+1), zero where kd falls outside 0..2 -- both outputs read the same voxel operand (the input slice).  4 x 9 x 4 = 144
+// MFMAs per wave and 4 input channels produce two slices instead of 2 x 108: 1.5x fewer MFMAs for the same result, bit-identical per
+// output (each output still sums its 27 x cin products in (ci, kd, ky, kx) order).  Same resident, tile-pipelined structure as
 // conv3d_mfma_stream_kernel.
 //
-// WREG (the 16-byte form; round 5: 3270 -> 3091 us on PixelViewWeight conv0 x480, 650 -> 611 us on CostRegNet conv0 x96, bit-identical,
-// profiles/r5_optins.jsonl): the 36 paired weights a lane multiplies with -- (j, ky, kx) of its
-// input channel kq and MFMA row m, the same for every tile of the launch -- live in 36 registers (read from global memory once per
-// workgroup) instead of an LDS slab read again for every tile.  The kernel then holds only the two halo buffers in LDS: 46 KB instead
-// of 56 KB in the 16-byte form = THREE workgroups per CU instead of two, and 72 instead of 108 LDS reads per 144 MFMAs.  The price is
-// ~88 instead of 52 VGPRs (no occupancy cost at 3 waves per SIMD) and a fully unrolled tile body.  Same products, same order.
+// Weights in registers (round 5, 16-byte form: 3270 -> 3091 us on PixelViewWeight conv0 x480, 650 -> 611 us on CostRegNet conv0 x96,
+// bit-identical, profiles/r5_optins.jsonl): the 36 paired weights a lane multiplies with -- (j, ky, kx) of its input channel kq and
+// MFMA row m, the same for every tile of the launch -- live in 36 registers (read from global memory once per workgroup) instead of
+// an LDS slab read again for every tile.  The kernel then holds only the two halo buffers in LDS: 46 KB instead of 56 KB in the
+// 16-byte form = THREE workgroups per CU instead of two, and 72 instead of 108 LDS reads per 144 MFMAs.  The price is ~88 instead of
+// 52 VGPRs (no occupancy cost at 3 waves per SIMD) and a fully unrolled tile body.  Same products, same order.
 constexpr int kPairWgsPerCu = 3;       // 45 KB of LDS each
-template <bool V16, bool WREG = false>
+template <bool V16>
 __global__ void __launch_bounds__(DMVS_BLOCK) conv3d_mfma_stream_pair_kernel(const dmvs_conv3d_desc d, int tiles_x, int tiles_y, int tiles_d) {
     constexpr int TX = 16, TY = 4, TD = 8, CK = 4;
     constexpr int IW = TX + 2, IH = TY + 2, ID = TD + 2;
     using HS = HaloSel<V16, ID, IH, IW>;
     constexpr int PLANE = HS::PLANE, IWP = HS::PITCH;
-    constexpr int WP = pad16mod32_3d(36 * 16);             // paired weights of one input channel: [j 4][ky 3][kx 3][16 rows]
     using Halo = typename HS::type;
-    __shared__ __attribute__((aligned(16))) float lds[2 * CK * PLANE + (WREG ? 0 : CK * WP)];
+    __shared__ __attribute__((aligned(16))) float lds[2 * CK * PLANE];
     DMVS_LDS_POISON(lds);
-    float* const s_w = lds + 2 * CK * PLANE;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int m = lane & 15, kq = lane >> 4;
-    const int vol = d.Din * d.Hin * d.Win, ovol = d.Dout * d.Hout * d.Wout;
+    const int ovol = d.Dout * d.Hout * d.Wout;
     const int ntiles = tiles_x * tiles_y * tiles_d * d.B;
 
     Halo halo;
     halo.init(tid, d.Hin, d.Win);
-    // paired weights of (input channel ci, slab position jt = (j, ky, kx), MFMA row): rows 0-7 take W[kd = j], rows 8-15 W[kd = j - 1]
-    auto paired = [&](int ci, int jt, int row) -> float {
-        const int j = jt / 9, t9 = jt - j * 9;
-        const int kd = row < 8 ? j : j - 1, co_ = row & 7;
-        return (ci < d.cin && kd >= 0 && kd <= 2 && co_ < d.cout) ? d.weight[(ci * 27 + kd * 9 + t9) * d.cout_pad + co_] : 0.0f;
-    };
-    float wreg[WREG ? 36 : 1];
-    if constexpr (WREG) {
+    float wreg[36];                     // this lane's weight operands: k = input channel kq, row m
 #pragma unroll
-        for (int jt = 0; jt < 36; ++jt) wreg[jt] = paired(kq, jt, m);      // this lane's A operands: k = input channel kq, row m
-    } else {
-        // paired weight slab, built once per workgroup from the [cin][27][cout_pad = 8] weights
-        for (int e = tid; e < CK * 36 * 16; e += DMVS_BLOCK) {
-            const int ci = e / (36 * 16), rem = e - ci * (36 * 16);
-            s_w[ci * WP + (rem >> 4) * 16 + (rem & 15)] = paired(ci, rem >> 4, rem & 15);
-        }
-    }
+    for (int jt = 0; jt < 36; ++jt) wreg[jt] = paired_weight(d, kq, jt, m);
     // epilogue constants (transposed accumulators: A = input pixels, B = the paired weights): this lane holds output slice
     // 2w + (m >> 3), channel m & 7, of the 4 consecutive voxels tx*16 + 4*kq + r of a row -- 16-byte stores
     const int co = m & 7, sl = m >> 3;
     const float sc = d.scale ? d.scale[co < d.cout ? co : 0] : 1.0f, sh = d.shift ? d.shift[co < d.cout ? co : 0] : 0.0f;
     const bool vec = (d.Wout & 3) == 0 && (((uintptr_t)d.out | (uintptr_t)d.residual) & 15) == 0;
-
-    auto stage = [&](int b, int td, int ty, int tx, float* buf) {
-        const int gx0 = tx * TX - 1, gy0 = ty * TY - 1, gd0 = td * TD - 1;
-        unsigned lo, him1;
-        Halo::bounds(gd0, gy0, gx0, d.Din, d.Hin, d.Win, lo, him1);
-        const float* origin = d.in + (size_t)b * d.cin * vol + ((long)gd0 * d.Hin + gy0) * d.Win + gx0;
-#pragma unroll
-        for (int ci = 0; ci < CK; ++ci) halo.stage(origin + (long)ci * vol, ci < d.cin, lo, him1, buf + ci * PLANE, wave);
-    };
-    auto decode = [&](int tile, int& b, int& td, int& ty, int& tx) {
-        tile = conv3d_xcd_tile(tile, ntiles, d.tune);
-        tx = tile % tiles_x; tile /= tiles_x;
-        ty = tile % tiles_y; tile /= tiles_y;
-        td = tile % tiles_d;
-        b = tile / tiles_d;
-    };
-    auto store = [&](const f32x4 (&a)[4], int sb, int std_, int sty, int stx) {
-        const int oxb = stx * TX + 4 * kq, od = std_ * TD + 2 * wave + sl;
+    auto store = [&](const f32x4 (&a)[4], const TilePos& p) {
+        const int oxb = p.tx * TX + 4 * kq, od = p.td * TD + 2 * wave + sl;
         if (oxb >= d.Wout || od >= d.Dout || co >= d.cout) return;
-        float* outb = d.out + (size_t)sb * d.cout * ovol;
-        const float* resb = d.residual ? d.residual + (size_t)sb * d.cout * ovol : nullptr;
+        float* outb = d.out + (size_t)p.b * d.cout * ovol;
+        const float* resb = d.residual ? d.residual + (size_t)p.b * d.cout * ovol : nullptr;
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) {
-            const int oy = sty * TY + mt;
+            const int oy = p.ty * TY + mt;
             if (oy >= d.Hout) continue;
             const int o = co * ovol + (od * d.Hout + oy) * d.Wout + oxb;
             f32x4 y;
@@ -457,58 +467,37 @@ __global__ void __launch_bounds__(DMVS_BLOCK) conv3d_mfma_stream_pair_kernel(con
     };
 
     int tile = blockIdx.x, cur = 0;
-    int b = 0, td = 0, ty = 0, tx = 0;
+    TilePos t = {0, 0, 0, 0}, prev = {-1, 0, 0, 0};
     f32x4 pend[4];                      // the previous tile's accumulators, stored one iteration late (after the barrier)
-    int pb = -1, ptd = 0, pty = 0, ptx = 0;
     if (tile < ntiles) {
-        decode(tile, b, td, ty, tx);
-        stage(b, td, ty, tx, lds);
+        t = conv3d_tile_pos(tile, ntiles, tiles_x, tiles_y, tiles_d, d.tune);
+        stage_chunk<CK>(halo, d, t.b, 0, t.td * TD - 1, t.ty * TY - 1, t.tx * TX - 1, lds, wave);
     }
     for (; tile < ntiles; tile += gridDim.x, cur ^= 1) {
-        DMVS_DMA_BARRIER();            // this tile's halo (and, first time, the paired weights) landed; the other buffer is free
-        int nb = 0, ntd = 0, nty = 0, ntx = 0;
+        DMVS_DMA_BARRIER();            // this tile's halo landed; the other buffer is free
+        TilePos next = {0, 0, 0, 0};
         if (tile + (int)gridDim.x < ntiles) {
-            decode(tile + gridDim.x, nb, ntd, nty, ntx);
-            stage(nb, ntd, nty, ntx, lds + (cur ^ 1) * (CK * PLANE));
+            next = conv3d_tile_pos(tile + gridDim.x, ntiles, tiles_x, tiles_y, tiles_d, d.tune);
+            stage_chunk<CK>(halo, d, next.b, 0, next.td * TD - 1, next.ty * TY - 1, next.tx * TX - 1, lds + (cur ^ 1) * (CK * PLANE), wave);
         }
-        if (pb >= 0) store(pend, pb, ptd, pty, ptx);
-        const float* s_in = lds + cur * (CK * PLANE);
+        if (prev.b >= 0) store(pend, prev);
         f32x4 acc[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) acc[i] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-        {
-            const float* wp = s_w + kq * WP + m;                                   // k = input channel kq
-            const float* ipb = s_in + kq * PLANE + (2 * wave) * (IH * IWP) + HS::X0 + m;      // halo slice 2w = input slice (2w - 1)
-            constexpr int kJUnroll = WREG ? 4 : 1;      // (register-resident weights are indexed by compile-time constants)
-#pragma unroll kJUnroll
-            for (int j = 0; j < 4; ++j) {
-#pragma unroll
-                for (int ky = 0; ky < 3; ++ky) {
-#pragma unroll
-                    for (int kx = 0; kx < 3; ++kx) {
-                        const float av = WREG ? wreg[WREG ? (j * 3 + ky) * 3 + kx : 0] : wp[((j * 3 + ky) * 3 + kx) * 16];
-#pragma unroll
-                        for (int mt = 0; mt < 4; ++mt) {
-                            const float bv = ipb[(j * IH + ky + mt) * IWP + kx];
-                            acc[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(bv, av, acc[mt], 0, 0, 0);      // D[voxel][(slice, cout)]
-                        }
-                    }
-                }
-            }
-        }
+        conv3d_pair_taps<IH, IWP>(lds + cur * (CK * PLANE) + kq * PLANE + (2 * wave) * (IH * IWP) + HS::X0 + m, wreg, acc);
 #pragma unroll
         for (int i = 0; i < 4; ++i) pend[i] = acc[i];
-        pb = b; ptd = td; pty = ty; ptx = tx;
-        b = nb; td = ntd; ty = nty; tx = ntx;
+        prev = t;
+        t = next;
     }
-    if (pb >= 0) store(pend, pb, ptd, pty, ptx);
+    if (prev.b >= 0) store(pend, prev);
 }
 
 // 5..8 input channels, cout <= 8 (CostRegNet conv1, 8 -> 8 at full resolution): the paired kernel above over TWO 4-channel chunks per
 // tile.  (Default since round 5: 1517 -> 983 us per 96 volumes on the MI355X, profiles/r5_optins.jsonl -- the generic kernel spends half of
 // its MFMA rows on padding, 216 MFMAs per 64 voxels against 144 here; DMVS_TUNE3D_NO_PAIR selects it for A/B.)  The pipeline item is a (tile, chunk) unit: while chunk c of a tile computes,
 // the next unit's 4-channel halo streams into the other LDS buffer; the accumulators live across a tile's two units and are stored one
-// unit late, after the next barrier.  Weights in registers (2 x 36 per lane, see WREG above): the kernel holds only the two halo
+// unit late, after the next barrier.  Weights in registers (2 x 36 per lane): the kernel holds only the two halo
 // buffers in LDS (46 KB, three workgroups per CU).  Each output still sums its products in (ci, kd, ky, kx) order: bit-identical to the
 // generic kernel.
 __global__ void __launch_bounds__(DMVS_BLOCK) conv3d_mfma_stream_pair8_kernel(const dmvs_conv3d_desc d, int tiles_x, int tiles_y, int tiles_d) {
@@ -522,48 +511,29 @@ __global__ void __launch_bounds__(DMVS_BLOCK) conv3d_mfma_stream_pair8_kernel(co
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int m = lane & 15, kq = lane >> 4;
-    const int vol = d.Din * d.Hin * d.Win, ovol = d.Dout * d.Hout * d.Wout;
+    const int ovol = d.Dout * d.Hout * d.Wout;
     const int ntiles = tiles_x * tiles_y * tiles_d * d.B;
 
     Halo halo;
     halo.init(tid, d.Hin, d.Win);
-    // this lane's A operands: input channel 4c + kq, MFMA row m: rows 0-7 take W[kd = j] (output slice 2w), rows 8-15 W[kd = j - 1] (2w + 1)
-    float wreg[NCH][36];
+    float wreg[NCH][36];                // this lane's weight operands: input channel 4c + kq, row m
 #pragma unroll
     for (int c = 0; c < NCH; ++c)
 #pragma unroll
-        for (int jt = 0; jt < 36; ++jt) {
-            const int ci = 4 * c + kq, j = jt / 9, t9 = jt - j * 9;
-            const int kd = m < 8 ? j : j - 1, co_ = m & 7;
-            wreg[c][jt] = (ci < d.cin && kd >= 0 && kd <= 2 && co_ < d.cout) ? d.weight[(ci * 27 + kd * 9 + t9) * d.cout_pad + co_] : 0.0f;
-        }
+        for (int jt = 0; jt < 36; ++jt) wreg[c][jt] = paired_weight(d, CK * c + kq, jt, m);
+    // epilogue constants (transposed accumulators: A = input pixels, B = the paired weights): this lane holds output slice
+    // 2w + (m >> 3), channel m & 7, of the 4 consecutive voxels tx*16 + 4*kq + r of a row -- 16-byte stores
     const int co = m & 7, sl = m >> 3;
     const float sc = d.scale ? d.scale[co < d.cout ? co : 0] : 1.0f, sh = d.shift ? d.shift[co < d.cout ? co : 0] : 0.0f;
     const bool vec = (d.Wout & 3) == 0 && (((uintptr_t)d.out | (uintptr_t)d.residual) & 15) == 0;
-
-    auto stage = [&](int b, int td, int ty, int tx, int c, float* buf) {
-        const int gx0 = tx * TX - 1, gy0 = ty * TY - 1, gd0 = td * TD - 1;
-        unsigned lo, him1;
-        Halo::bounds(gd0, gy0, gx0, d.Din, d.Hin, d.Win, lo, him1);
-        const float* origin = d.in + ((size_t)b * d.cin + 4 * c) * vol + ((long)gd0 * d.Hin + gy0) * d.Win + gx0;
-#pragma unroll
-        for (int ci = 0; ci < CK; ++ci) halo.stage(origin + (long)ci * vol, 4 * c + ci < d.cin, lo, him1, buf + ci * PLANE, wave);
-    };
-    auto decode = [&](int tile, int& b, int& td, int& ty, int& tx) {
-        tile = conv3d_xcd_tile(tile, ntiles, d.tune);
-        tx = tile % tiles_x; tile /= tiles_x;
-        ty = tile % tiles_y; tile /= tiles_y;
-        td = tile % tiles_d;
-        b = tile / tiles_d;
-    };
-    auto store = [&](const f32x4 (&a)[4], int sb, int std_, int sty, int stx) {
-        const int oxb = stx * TX + 4 * kq, od = std_ * TD + 2 * wave + sl;
+    auto store = [&](const f32x4 (&a)[4], const TilePos& p) {
+        const int oxb = p.tx * TX + 4 * kq, od = p.td * TD + 2 * wave + sl;
         if (oxb >= d.Wout || od >= d.Dout || co >= d.cout) return;
-        float* outb = d.out + (size_t)sb * d.cout * ovol;
-        const float* resb = d.residual ? d.residual + (size_t)sb * d.cout * ovol : nullptr;
+        float* outb = d.out + (size_t)p.b * d.cout * ovol;
+        const float* resb = d.residual ? d.residual + (size_t)p.b * d.cout * ovol : nullptr;
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) {
-            const int oy = sty * TY + mt;
+            const int oy = p.ty * TY + mt;
             if (oy >= d.Hout) continue;
             const int o = co * ovol + (od * d.Hout + oy) * d.Wout + oxb;
             f32x4 y;
@@ -579,51 +549,38 @@ __global__ void __launch_bounds__(DMVS_BLOCK) conv3d_mfma_stream_pair8_kernel(co
             }
         }
     };
-    auto chunk_mfmas = [&](const float* s_in, const float (&w)[36], f32x4 (&acc)[4]) __attribute__((always_inline)) {
-        const float* ipb = s_in + kq * PLANE + (2 * wave) * (IH * IWP) + HS::X0 + m;      // halo slice 2w = input slice (2w - 1)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-                for (int kx = 0; kx < 3; ++kx)
-#pragma unroll
-                    for (int mt = 0; mt < 4; ++mt)
-                        acc[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(ipb[(j * IH + ky + mt) * IWP + kx], w[(j * 3 + ky) * 3 + kx], acc[mt], 0, 0, 0);
-    };
 
     int tile = blockIdx.x, cur = 0;
-    int b = 0, td = 0, ty = 0, tx = 0;
+    TilePos t = {0, 0, 0, 0}, prev = {-1, 0, 0, 0};
     f32x4 acc[4], pend[4];              // this tile's accumulators (live across its two units); the previous tile's, not stored yet
-    int pb = -1, ptd = 0, pty = 0, ptx = 0;
     if (tile < ntiles) {
-        decode(tile, b, td, ty, tx);
-        stage(b, td, ty, tx, 0, lds);
+        t = conv3d_tile_pos(tile, ntiles, tiles_x, tiles_y, tiles_d, d.tune);
+        stage_chunk<CK>(halo, d, t.b, 0, t.td * TD - 1, t.ty * TY - 1, t.tx * TX - 1, lds, wave);
     }
     for (; tile < ntiles; tile += gridDim.x) {
         // ---- unit (tile, chunk 0): chunk 1 of the same tile streams in meanwhile
         DMVS_DMA_BARRIER();
-        stage(b, td, ty, tx, 1, lds + (cur ^ 1) * (CK * PLANE));
-        if (pb >= 0) store(pend, pb, ptd, pty, ptx);
+        stage_chunk<CK>(halo, d, t.b, CK, t.td * TD - 1, t.ty * TY - 1, t.tx * TX - 1, lds + (cur ^ 1) * (CK * PLANE), wave);
+        if (prev.b >= 0) store(pend, prev);
 #pragma unroll
         for (int i = 0; i < 4; ++i) acc[i] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-        chunk_mfmas(lds + cur * (CK * PLANE), wreg[0], acc);
+        conv3d_pair_taps<IH, IWP>(lds + cur * (CK * PLANE) + kq * PLANE + (2 * wave) * (IH * IWP) + HS::X0 + m, wreg[0], acc);
         cur ^= 1;
         // ---- unit (tile, chunk 1): chunk 0 of the workgroup's next tile streams in meanwhile
         DMVS_DMA_BARRIER();
-        int nb = 0, ntd = 0, nty = 0, ntx = 0;
+        TilePos next = {0, 0, 0, 0};
         if (tile + (int)gridDim.x < ntiles) {
-            decode(tile + gridDim.x, nb, ntd, nty, ntx);
-            stage(nb, ntd, nty, ntx, 0, lds + (cur ^ 1) * (CK * PLANE));
+            next = conv3d_tile_pos(tile + gridDim.x, ntiles, tiles_x, tiles_y, tiles_d, d.tune);
+            stage_chunk<CK>(halo, d, next.b, 0, next.td * TD - 1, next.ty * TY - 1, next.tx * TX - 1, lds + (cur ^ 1) * (CK * PLANE), wave);
         }
-        chunk_mfmas(lds + cur * (CK * PLANE), wreg[1], acc);
+        conv3d_pair_taps<IH, IWP>(lds + cur * (CK * PLANE) + kq * PLANE + (2 * wave) * (IH * IWP) + HS::X0 + m, wreg[1], acc);
         cur ^= 1;
 #pragma unroll
         for (int i = 0; i < 4; ++i) pend[i] = acc[i];
-        pb = b; ptd = td; pty = ty; ptx = tx;
-        b = nb; td = ntd; ty = nty; tx = ntx;
+        prev = t;
+        t = next;
     }
-    if (pb >= 0) store(pend, pb, ptd, pty, ptx);
+    if (prev.b >= 0) store(pend, prev);
 }
 
 // S = 2: the stride-2 layers of CostRegNet_small (conv2 8 -> 16, conv4 16 -> 32, reference module.py:428-433) as the same
@@ -650,12 +607,8 @@ __global__ void __launch_bounds__(DMVS_BLOCK) conv3d_mfma_kernel(const dmvs_conv
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int m = lane & 15, kq = lane >> 4;
-    int tile = conv3d_xcd_tile((int)blockIdx.x, (int)gridDim.x, d.tune);
-    const int tx = tile % tiles_x; tile /= tiles_x;
-    const int ty = tile % tiles_y; tile /= tiles_y;
-    const int td = tile % tiles_d;
-    const int b = tile / tiles_d;
-    const int x0 = tx * TX, y0 = ty * TY, d0 = td * TD;
+    const TilePos t = conv3d_tile_pos((int)blockIdx.x, (int)gridDim.x, tiles_x, tiles_y, tiles_d, d.tune);
+    const int b = t.b, x0 = t.tx * TX, y0 = t.ty * TY, d0 = t.td * TD;
     const int nbase = blockIdx.y * NW;
     const int vol = d.Din * d.Hin * d.Win, ovol = d.Dout * d.Hout * d.Wout;
 
@@ -740,12 +693,8 @@ __global__ void __launch_bounds__(DMVS_BLOCK) conv3d_c1_kernel(const dmvs_conv3d
     __shared__ __attribute__((aligned(16))) float lds[2 * PLANE];
     DMVS_LDS_POISON(lds);
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int tile = conv3d_xcd_tile((int)blockIdx.x, (int)gridDim.x, d.tune);
-    const int tx = tile % tiles_x; tile /= tiles_x;
-    const int ty = tile % tiles_y; tile /= tiles_y;
-    const int td = tile % tiles_d;
-    const int b = tile / tiles_d;
-    const int x0 = tx * TX, y0 = ty * TY, d0 = td * TD;
+    const TilePos t = conv3d_tile_pos((int)blockIdx.x, (int)gridDim.x, tiles_x, tiles_y, tiles_d, d.tune);
+    const int b = t.b, x0 = t.tx * TX, y0 = t.ty * TY, d0 = t.td * TD;
     const int vol = d.Din * d.Hin * d.Win;
     const int lx = (tid & 3) * 4, ly = ((tid >> 2) & 7) * 2, ld = (tid >> 5) * 2;
 
@@ -1092,13 +1041,9 @@ __global__ void __launch_bounds__(DMVS_BLOCK) deconv3d_mfma_kernel(const dmvs_co
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int m = lane & 15, kq = lane >> 4;
-    int tile = conv3d_xcd_tile((int)blockIdx.x, (int)gridDim.x, d.tune);
-    const int tx = tile % tiles_x; tile /= tiles_x;
-    const int ty = tile % tiles_y; tile /= tiles_y;
-    const int td = tile % tiles_d;
-    const int b = tile / tiles_d;
-    const int vol = d.Din * d.Hin * d.Win, ovol = d.Dout * d.Hout * d.Wout;
-    const int jx0 = tx * TX, jy0 = ty * TY, jd0 = td * TD;
+    const TilePos t = conv3d_tile_pos((int)blockIdx.x, (int)gridDim.x, tiles_x, tiles_y, tiles_d, d.tune);
+    const int b = t.b, jx0 = t.tx * TX, jy0 = t.ty * TY, jd0 = t.td * TD;
+    const int ovol = d.Dout * d.Hout * d.Wout;
 
     // output channels co_base .. co_base + 7 (blockIdx.y: wider layers -- CostRegNet conv6, 32 -> 16 -- take 8 channels per
     // workgroup); input channels in chunks of CK (single-buffered: 2 chunks at most in the reference's networks)
@@ -1114,6 +1059,7 @@ __global__ void __launch_bounds__(DMVS_BLOCK) deconv3d_mfma_kernel(const dmvs_co
     for (int c0 = 0; c0 < d.cin; c0 += CK) {
     if (c0 > 0) __syncthreads();        // every wave is done with the previous chunk's halo and slabs
     {
+        const int vol = d.Din * d.Hin * d.Win;
         unsigned lo, him1;
         Halo::bounds(jd0, jy0, jx0, d.Din, d.Hin, d.Win, lo, him1);
         const float* origin = d.in + ((size_t)b * d.cin + c0) * vol + ((long)jd0 * d.Hin + jy0) * d.Win + jx0;
@@ -1259,11 +1205,11 @@ extern "C" int dmvs_conv3d_f32(const dmvs_conv3d_desc* dp, void* stream) {
         if (!(d.tune & DMVS_TUNE3D_NO_PAIR) && d.cin <= 4 && d.cout <= 8 && d.cout_pad == 8) {      // 4 -> 8 layers: two output depth slices share the 16 MFMA rows
             const int tiles_d8 = (d.Dout + 7) / 8;
             if ((long)tiles_x * tiles_y * tiles_d8 * d.B >= 512) {
-                if (v16) {      // 16-byte halo pieces, the lane's 36 paired weights in registers: 46 KB of LDS, resident count from the occupancy query
-                    static const int resident = dmvs_resident_workgroups(reinterpret_cast<const void*>(conv3d_mfma_stream_pair_kernel<true, true>));
-                    hipLaunchKernelGGL((conv3d_mfma_stream_pair_kernel<true, true>), dim3((unsigned)resident, 1), block, 0, st, d, tiles_x, tiles_y, tiles_d8);
+                if (v16) {      // 16-byte halo pieces: 46 KB of LDS, resident count from the occupancy query
+                    static const int resident = dmvs_resident_workgroups(reinterpret_cast<const void*>(conv3d_mfma_stream_pair_kernel<true>));
+                    hipLaunchKernelGGL((conv3d_mfma_stream_pair_kernel<true>), dim3((unsigned)resident, 1), block, 0, st, d, tiles_x, tiles_y, tiles_d8);
                 } else {
-                    hipLaunchKernelGGL((conv3d_mfma_stream_pair_kernel<false, false>), dim3((unsigned)(256 * kPairWgsPerCu), 1), block, 0, st, d, tiles_x, tiles_y, tiles_d8);
+                    hipLaunchKernelGGL((conv3d_mfma_stream_pair_kernel<false>), dim3((unsigned)(256 * kPairWgsPerCu), 1), block, 0, st, d, tiles_x, tiles_y, tiles_d8);
                 }
                 return dmvs_launch_status();
             }

@@ -26,40 +26,54 @@ SHAPES = [  # name, N, cin, cout, k, stride, H, W
 ]
 
 
-SHAPES3D = [  # name, N, cin, cout, D, H, W, stride
-    ("pvw conv0 4->8 (5 views)", 80, 4, 8, 48, 64, 80, 1), ("costreg conv0 4->8", 16, 4, 8, 48, 64, 80, 1),
-    ("costreg conv1 8->8", 16, 8, 8, 48, 64, 80, 1), ("costreg conv3 16->16", 16, 16, 16, 24, 32, 40, 1),
-    ("costreg conv5 32->32", 16, 32, 32, 12, 16, 20, 1), ("costreg prob 8->1 B96", 96, 8, 1, 48, 64, 80, 1),
-    ("costreg conv0 4->8 B96", 96, 4, 8, 48, 64, 80, 1), ("costreg conv1 8->8 B96", 96, 8, 8, 48, 64, 80, 1),
+SHAPES3D = [  # name, N, cin, cout, D, H, W, stride, transposed
+    ("pvw conv0 4->8 (5 views)", 80, 4, 8, 48, 64, 80, 1, False), ("costreg conv0 4->8", 16, 4, 8, 48, 64, 80, 1, False),
+    ("costreg conv1 8->8", 16, 8, 8, 48, 64, 80, 1, False), ("costreg conv3 16->16", 16, 16, 16, 24, 32, 40, 1, False),
+    ("costreg conv5 32->32", 16, 32, 32, 12, 16, 20, 1, False), ("costreg prob 8->1 B96", 96, 8, 1, 48, 64, 80, 1, False),
+    ("costreg conv0 4->8 B96", 96, 4, 8, 48, 64, 80, 1, False), ("costreg conv1 8->8 B96", 96, 8, 8, 48, 64, 80, 1, False),
+    ("costreg conv2 8->16 s2 B96", 96, 8, 16, 48, 64, 80, 2, False), ("costreg conv4 16->32 s2 B96", 96, 16, 32, 24, 32, 40, 2, False),
+    ("costreg conv6 32->16 T B96", 96, 32, 16, 12, 16, 20, 2, True), ("costreg conv7 16->8 T B96", 96, 16, 8, 24, 32, 40, 2, True),
+    ("pvw conv1 8->1 N480", 480, 8, 1, 48, 64, 80, 1, False),
 ]
 
 
 def main():
+    from diffmvs_amd import _lib
     o = K.Ops.for_device("cuda:0")
     if os.environ.get("CONV_LIB"):
-        from diffmvs_amd import _lib
         o = K.Ops(_lib.Lib(os.path.abspath(os.environ["CONV_LIB"])), "cuda:0")
+    # CONV_LIB_B: a second library; every 3-D row then runs on both in alternating rounds (A/B inside one process, median per library)
+    libs = [o] + ([K.Ops(_lib.Lib(os.path.abspath(os.environ["CONV_LIB_B"])), "cuda:0")] if os.environ.get("CONV_LIB_B") else [])
+    rounds = 5 if len(libs) > 1 else 1
     g3 = torch.Generator(device="cuda").manual_seed(1)      # (inputs drawn on the device: the N = 576 tensors take seconds on the host)
-    for name, N, cin, cout, D, H, W, s in SHAPES3D:
+    for name, N, cin, cout, D, H, W, s, transposed in SHAPES3D:
         if os.environ.get("CONV_2D_ONLY") or (os.environ.get("CONV_ONLY") and os.environ["CONV_ONLY"] not in name):
             continue
         x = torch.randn(N, cin, D, H, W, generator=g3, device="cuda")
-        w = torch.randn(cout, cin, 3, 3, 3, generator=g3, device="cuda") * 0.1
-        pc = K.pack_conv3d(w, None, stride=s)
-        for _ in range(3):
-            y = o.conv3d(pc, x, act=K.ACT_RELU)
+        w = torch.randn(*((cin, cout) if transposed else (cout, cin)), 3, 3, 3, generator=g3, device="cuda") * 0.1
+        pc = K.pack_conv3d(w, None, stride=s, transposed=transposed)
+        for ops in libs:
+            for _ in range(3):
+                y = ops.conv3d(pc, x, act=K.ACT_RELU)
         torch.cuda.synchronize()
-        st, en = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        st.record()
-        for _ in range(10):
-            o.conv3d(pc, x, act=K.ACT_RELU)
-        en.record()
-        torch.cuda.synchronize()
-        us = st.elapsed_time(en) * 100.0
-        flops = 2.0 * y.numel() * cin * 27
+        times = [[] for _ in libs]
+        for _ in range(rounds):
+            for ops, ts in zip(libs, times):
+                st, en = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                st.record()
+                for _ in range(10):
+                    ops.conv3d(pc, x, act=K.ACT_RELU)
+                en.record()
+                torch.cuda.synchronize()
+                ts.append(st.elapsed_time(en) * 100.0)
+        us = sorted(times[0])[rounds // 2]
+        flops = 2.0 * (x.numel() * cout if transposed else y.numel() * cin) * 27
         gb = 4.0 * (x.numel() + y.numel()) / 1e9
-        print(json.dumps({"layer": name, "us": round(us, 1), "TFLOPs": round(flops / us / 1e6, 1), "GB": round(gb, 3),
-                          "TBs": round(gb / us * 1e3, 2)}))
+        row = {"layer": name, "us": round(us, 1), "TFLOPs": round(flops / us / 1e6, 1), "GB": round(gb, 3), "TBs": round(gb / us * 1e3, 2)}
+        if len(libs) > 1:
+            us_b = sorted(times[1])[rounds // 2]
+            row.update({"us_b": round(us_b, 1), "ratio_b_over_a": round(us_b / us, 4)})
+        print(json.dumps(row), flush=True)
     if os.environ.get("CONV_3D_ONLY"):
         return
     g = torch.Generator(device="cuda").manual_seed(0)
