@@ -127,6 +127,13 @@ def main(argv=None, device=None):
     ap.add_argument("--geo_pixel_thres", type=float, default=1.0, help="reprojection error threshold in pixels")
     ap.add_argument("--geo_depth_thres", type=float, default=0.01, help="relative depth error threshold")
     ap.add_argument("--photo_thres", type=float, nargs="+", default=[0.3, 0.0, 0.0], help="confidence threshold per stage")
+    ap.add_argument("--normals", action="store_true", help="with --filter: the fused PLY also carries an oriented normal (nx ny nz) per point, from a "
+                    "plane fitted in inverse depth on the GPU; adds normals[scene] (slot totals) to the result")
+    ap.add_argument("--normal_radius", type=int, default=2, help="--normals: the fit's window is (2 r + 1)^2 pixels, r = 1..4")
+    ap.add_argument("--normal_jump", type=float, default=0.02, help="--normals: neighbours whose inverse depth differs by more than this fraction of the pixel's are left out of its fit")
+    ap.add_argument("--normal_min_pts", type=int, default=5, help="--normals: pixels with fewer neighbours in the fit get no normal")
+    ap.add_argument("--max_view_angle", type=float, default=None, help="with --filter (implies --normals): leave points out of the cloud that have no normal or "
+                    "are seen at more than this many degrees off their normal")
     ap.add_argument("--gt_ply", default=None, help="with --filter: score every fused cloud against this ground-truth PLY ('{scene}' is substituted) "
                     "with diffmvs_amd.cloud_eval; adds cloud_metrics[scene] to the result")
     ap.add_argument("--gt_transform", default=None, help="--gt_ply: 4x4 text file that moves the fused cloud into the ground truth's frame ('{scene}' is substituted)")
@@ -185,6 +192,9 @@ def main(argv=None, device=None):
         from . import fusion
         for scene in mine:      # the per-dataset protocol of test.py:298-367
             kw = fusion.scene_protocol(a.dataset, scene, a.outdir, a.geo_mask_thres, a.geo_pixel_thres, a.geo_depth_thres, a.photo_thres)
+            if a.normals or a.max_view_angle is not None:
+                kw.update(normals=True, normal_radius=a.normal_radius, normal_jump=a.normal_jump, normal_min_pts=a.normal_min_pts,
+                          max_view_angle=a.max_view_angle, stats=res.setdefault("normals", {}).setdefault(scene, {}))
             n = fusion.filter_depth(os.path.join(a.testpath, scene), os.path.join(a.outdir, scene), method=a.method, device=device, **kw)
             res.setdefault("fused_points", {})[scene] = n
             res.setdefault("ply", {})[scene] = kw["plyfilename"]

@@ -301,16 +301,23 @@ def abs_rel_error(depth_est: torch.Tensor, depth_gt: torch.Tensor, mask: torch.T
 
 
 # ------------------------------------------------------------------------------------------ PLY
-def write_ply(filename: str, xyz: np.ndarray, rgb: np.ndarray) -> None:
+def write_ply(filename: str, xyz: np.ndarray, rgb: np.ndarray, normals: np.ndarray | None = None) -> None:
     """binary little-endian PLY with x y z (float32) red green blue (uint8) per vertex: what plyfile writes for
-    filter.py:208-227"""
+    filter.py:208-227.  With normals [N,3] the vertex is x y z nx ny nz (float32) red green blue: the property names and the order
+    MeshLab, Open3D and PoissonRecon expect."""
     n = xyz.shape[0]
-    v = np.empty(n, dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+    if normals is not None and tuple(normals.shape) != (n, 3):
+        raise ValueError(f"write_ply: {n} vertices need normals of shape ({n}, 3), got {tuple(normals.shape)}")
+    nrm = [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")] if normals is not None else []
+    v = np.empty(n, dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4")] + nrm + [("red", "u1"), ("green", "u1"), ("blue", "u1")])
     v["x"], v["y"], v["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+    if normals is not None:
+        v["nx"], v["ny"], v["nz"] = normals[:, 0], normals[:, 1], normals[:, 2]
     v["red"], v["green"], v["blue"] = rgb[:, 0], rgb[:, 1], rgb[:, 2]
     with open(filename, "wb") as f:
-        f.write(("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
-                 "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n" % n).encode("ascii"))
+        f.write(("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n%s"
+                 "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n"
+                 % (n, "".join("property float %s\n" % k for k, _ in nrm))).encode("ascii"))
         f.write(v.tobytes())
 
 
@@ -318,9 +325,9 @@ _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short":
               "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
 
 
-def read_ply(filename: str):
-    """-> (xyz float32 [N,3], rgb uint8 [N,3] or None).  Reads `binary_little_endian` and `ascii` PLY files with any scalar
-    vertex properties in any order (normals, confidence, ...); other elements (faces) are skipped, list properties are allowed
+def read_ply(filename: str, with_normals: bool = False):
+    """-> (xyz float32 [N,3], rgb uint8 [N,3] or None); with_normals: -> (xyz, rgb, normals float32 [N,3] or None), the vertex
+    properties nx ny nz.  Reads `binary_little_endian` and `ascii` PLY files with any scalar vertex properties in any order (normals, confidence, ...); other elements (faces) are skipped, list properties are allowed
     in them only.  The inverse of write_ply."""
     with open(filename, "rb") as f:
         data = f.read()
@@ -402,4 +409,9 @@ def read_ply(filename: str):
         if all(k in vertex for k in keys):
             rgb = np.stack([np.asarray(vertex[k]).astype(np.uint8) for k in keys], -1)
             break
-    return np.ascontiguousarray(xyz), rgb
+    if not with_normals:
+        return np.ascontiguousarray(xyz), rgb
+    normals = None
+    if all(k in vertex for k in ("nx", "ny", "nz")):
+        normals = np.ascontiguousarray(np.stack([np.asarray(vertex[k], dtype=np.float32) for k in ("nx", "ny", "nz")], -1))
+    return np.ascontiguousarray(xyz), rgb, normals

@@ -135,10 +135,27 @@ def unproject(depth: np.ndarray, K: np.ndarray, E: np.ndarray, mask: np.ndarray)
     return np.matmul(np.linalg.inv(E), np.vstack((xyz_ref, np.ones_like(x))))[:3].transpose((1, 0))
 
 
+def view_normals(ops: Ops, depth: np.ndarray, mask: np.ndarray, K, E, radius=2, rel_jump=0.02, min_pts=5):
+    """one view (numpy in, numpy out): the oriented world normals of a depth map from dmvs_depth_normals_f32 (include/dmvs.h), a plane
+    fitted in inverse depth over the pixels of `mask`.  depth [H,W] (cast to fp32), mask [H,W] bool or None, K [3,3], E [4,4].
+    -> (out [H,W,4] fp32: normal x y z and the cosine to the viewing ray, zeros where there is no normal; counts [4] int64: the slots)"""
+    d = torch.from_numpy(np.ascontiguousarray(depth, dtype=np.float32)[None]).to(ops.device)
+    m = None if mask is None else torch.from_numpy(np.ascontiguousarray(mask, dtype=np.uint8)[None]).to(ops.device)
+    out, counts = ops.depth_normals(d, m, np.asarray(K)[None], np.asarray(E)[None], radius, rel_jump, min_pts)
+    return out[0].cpu().numpy(), counts[0].cpu().numpy()
+
+
 def filter_depth(pair_folder, out_folder, plyfilename, geo_mask_thres=3, geo_pixel_thres=1.0, geo_depth_thres=0.01,
-                 photo_thres=(0.3, 0.5, 0.5), method="casdiffmvs", dataset="dtu", scan=None, device="cuda:0", ops: Ops | None = None) -> int:
+                 photo_thres=(0.3, 0.5, 0.5), method="casdiffmvs", dataset="dtu", scan=None, device="cuda:0", ops: Ops | None = None,
+                 normals=False, normal_radius=2, normal_jump=0.02, normal_min_pts=5, max_view_angle=None, stats: dict | None = None) -> int:
     """filter.py:95-227 (dataset != 'tank') / :261-441 (dataset == 'tank': `scan` picks the dynamic parameters) over one
-    scene's output tree; writes mask/*.png and the fused point cloud.  -> number of fused points."""
+    scene's output tree; writes mask/*.png and the fused point cloud.  -> number of fused points.
+    normals: the PLY also carries nx ny nz, the oriented normal of every point from view_normals() on the view's averaged depth (fp32)
+    over its `final` mask; a point whose pixel got no normal carries (0, 0, 0).  max_view_angle (degrees; implies normals): points
+    without a normal, or seen at more than this angle off their normal (cos < cos(angle)), are left out of the CLOUD; the masks stay
+    the reference's.  stats: a dict that receives {"slots": the four slot totals of include/dmvs.h over all views, "no_normal": written
+    points that carry (0, 0, 0), "dropped": points max_view_angle left out} when normals are on.  With the defaults every output is
+    what it was without these options."""
     from PIL import Image
     ops = ops or Ops.for_device(device)
     if os.path.dirname(plyfilename):
@@ -154,7 +171,10 @@ def filter_depth(pair_folder, out_folder, plyfilename, geo_mask_thres=3, geo_pix
             cache[v] = (np.ascontiguousarray(IO.read_pfm(os.path.join(out_folder, f"depth_est/{v:0>8}.pfm"))[0]), k, e, dmax, dmin)
         return cache[v]
 
-    verts, cols = [], []
+    want_normals = bool(normals) or max_view_angle is not None
+    cos_min = None if max_view_angle is None else float(np.cos(np.deg2rad(np.float64(max_view_angle))))
+    verts, cols, nrms = [], [], []
+    slots, no_normal, dropped = np.zeros(_lib.NORMAL_SLOTS, np.int64), 0, 0
     os.makedirs(os.path.join(out_folder, "mask"), exist_ok=True)
     for ref_view, src_views in pairs:
         rd, rk, re_, dmax, dmin = view(ref_view)
@@ -165,8 +185,22 @@ def filter_depth(pair_folder, out_folder, plyfilename, geo_mask_thres=3, geo_pix
                                            geo_depth_thres, method, dynamic)
         for name, m in (("photo", photo), ("geo", geo), ("final", final)):
             Image.fromarray(m.astype(np.uint8) * 255).save(os.path.join(out_folder, f"mask/{ref_view:0>8}_{name}.png"))
-        verts.append(unproject(avg, rk, re_, final))
-        cols.append((img[final] * 255).astype(np.uint8))
+        pts, col = unproject(avg, rk, re_, final), (img[final] * 255).astype(np.uint8)
+        if want_normals:
+            nrm, cnt = view_normals(ops, avg, final, rk, re_, normal_radius, normal_jump, normal_min_pts)
+            nrm = nrm[final]
+            slots += cnt
+            has = (nrm[:, :3] != 0).any(1)                # (a written normal has unit length)
+            if cos_min is not None:
+                keep = has & (nrm[:, 3].astype(np.float64) >= cos_min)
+                dropped += int((~keep).sum())
+                pts, col, nrm, has = pts[keep], col[keep], nrm[keep], has[keep]
+            no_normal += int((~has).sum())
+            nrms.append(nrm[:, :3])
+        verts.append(pts)
+        cols.append(col)
     xyz, rgb = np.concatenate(verts, 0), np.concatenate(cols, 0)
-    IO.write_ply(plyfilename, xyz.astype(np.float32), rgb)
+    IO.write_ply(plyfilename, xyz.astype(np.float32), rgb, np.concatenate(nrms, 0) if want_normals else None)
+    if want_normals and stats is not None:
+        stats.update(slots=[int(v) for v in slots], no_normal=no_normal, dropped=dropped)
     return int(xyz.shape[0])

@@ -930,3 +930,46 @@ class Ops:
         self._call("dmvs_cloud_splat_sum_f32", _ptr(points), N, self._transform_arg(transform), v.ctypes.data_as(C.c_void_p), V, H, W, float(radius),
                    float(r_min), float(r_max), float(tau), float(scale), int(blocks), _ptr(zbuf), _ptr(total), _ptr(cnt), self.stream())
         return total, cnt
+
+    # ------------------------------------------------------------------ oriented normals of a depth map (diffmvs_amd/fusion.py)
+    @staticmethod
+    def normal_cams(K, E):
+        """K [B,3,3], E [B,4,4] (world -> camera) -> the HOST [B,27] fp64 table of dmvs_depth_normals_f32: K | inv(K), formed here in
+        fp64 | R = E[:3,:3], each row-major"""
+        import numpy as np
+        K, E = (np.asarray(m.detach().cpu().numpy() if torch.is_tensor(m) else m, np.float64) for m in (K, E))
+        if K.ndim != 3 or K.shape[1:] != (3, 3) or E.shape != (K.shape[0], 4, 4):
+            raise _lib.DmvsError(f"depth_normals: K must be [B,3,3] and E [B,4,4], got {K.shape} and {E.shape}")
+        B = K.shape[0]
+        if not (np.isfinite(K).all() and np.isfinite(E).all()):
+            raise _lib.DmvsError("depth_normals: a camera matrix with a non-finite entry")
+        try:
+            Kinv = np.linalg.inv(K) if B else K
+        except np.linalg.LinAlgError as e:
+            raise _lib.DmvsError("depth_normals: a singular intrinsic matrix") from e
+        return np.ascontiguousarray(np.concatenate([K.reshape(B, 9), Kinv.reshape(B, 9), E[:, :3, :3].reshape(B, 9)], 1))
+
+    def depth_normals(self, depth, valid, K, E, radius=2, rel_jump=0.02, min_pts=5):
+        """dmvs_depth_normals_f32 (include/dmvs.h): a plane fitted in inverse depth to every pixel's (2 radius + 1)^2 window.  depth [B,H,W]
+        fp32; valid None or [B,H,W] uint8 / bool; K [B,3,3], E [B,4,4] on the host (or a ready normal_cams table [B,27]).
+        -> (out [B,H,W,4] fp32: the world normal and the cosine to the viewing ray, zeros where there is none; counts [B,4] int64: centre
+        not usable, support degenerate, fit rejected, normals written)"""
+        import numpy as np
+        if valid is not None and valid.dtype == torch.bool:
+            valid = valid.view(torch.uint8)
+        self._chk_typed("depth_normals", (depth, torch.float32), (valid, torch.uint8))
+        if depth.dim() != 3 or (valid is not None and valid.shape != depth.shape):
+            raise _lib.DmvsError(f"depth_normals: depth (and the mask) must be [B,H,W], got {tuple(depth.shape)}"
+                                 + (f" and {tuple(valid.shape)}" if valid is not None else ""))
+        B, H, W = (int(s) for s in depth.shape)
+        cams = np.ascontiguousarray(K, np.float64) if E is None else self.normal_cams(K, E)
+        if cams.shape != (B, _lib.NORMAL_CAM_DOUBLES):
+            raise _lib.DmvsError(f"depth_normals: {B} depth maps need a [{B},{_lib.NORMAL_CAM_DOUBLES}] camera table, got {cams.shape}")
+        if not 1 <= int(radius) <= _lib.NORMAL_MAX_RADIUS:
+            raise _lib.DmvsError(f"depth_normals: radius {radius}; 1..{_lib.NORMAL_MAX_RADIUS} are supported")
+        fresh = torch.empty if B * H * W > 0 else torch.zeros      # (the library writes both, unless there is nothing to do)
+        out = fresh((B, H, W, 4), dtype=torch.float32, device=self.device)
+        counts = fresh((B, _lib.NORMAL_SLOTS), dtype=torch.int64, device=self.device)
+        self._call("dmvs_depth_normals_f32", _ptr(depth), _ptr(valid), cams.ctypes.data_as(C.c_void_p), B, H, W, int(radius), float(rel_jump),
+                   int(min_pts), _ptr(out), _ptr(counts), self.stream())
+        return out, counts

@@ -646,6 +646,45 @@ int dmvs_cloud_splat_sum_f32(const float* points, int64_t N, const double* trans
                              double radius, double r_min, double r_max, double tau, double scale, int32_t blocks, const float* zbuf,
                              uint64_t* sum, int32_t* cnt, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Oriented normals of a depth map (added under ABI 4, additive; diffmvs_amd/fusion.py): for a plane n.X = rho seen by a pinhole camera
+ * 1 / depth is an affine function of the pixel, 1/d = (K^T)^-1 (n / rho) . (u, v, 1), so the plane through a pixel's neighbourhood is a
+ * LINEAR least-squares fit in inverse depth on integer pixel offsets: an exact integer normal matrix, three fp64 sums, no eigen-solver.
+ *
+ * depth [B,H,W] fp32 (device);  valid: NULL or [B,H,W] uint8 (device);  cams: HOST [B, DMVS_NORMAL_CAM_DOUBLES] doubles per view:
+ * K row-major (9) | inv(K) (9, formed by the caller) | R = E[:3,:3], world -> camera (9).  Views go DMVS_NORMAL_VIEW_CHUNK per launch as
+ * kernel arguments.  out [B,H,W,4] fp32: the world normal x, y, z and the cosine between it and the ray back to the camera.
+ * counts [B, DMVS_NORMAL_SLOTS] int64 (device, zeroed here).
+ * Per pixel (y, x), pixel centres at integer coordinates, IEEE fp64 in exactly this order, no contraction:
+ *   usable(j): (valid is NULL or valid[j] != 0) and depth[j] finite and > 0;  then w_j = 1.0 / (double)depth[j].
+ *   The centre c is not usable: slot 0, four zeros.
+ *   Support: the offsets dy = -r .. r (outer), dx = -r .. r (inner) that are inside the image, usable and have
+ *     fabs(d_j) <= rel_jump * w_c  with  d_j = w_j - w_c  (the centre always is); any other tap is skipped.
+ *   Integer sums over the support (exact): n, Sx = sum dx, Sy = sum dy, Sxx, Sxy, Syy.
+ *   fp64 sums in walk order: Tw += d_j,  Tx += (double)dx * d_j,  Ty += (double)dy * d_j.
+ *   Integer cofactors:  C00 = Syy n - Sy^2   C01 = -(Sxy n - Sx Sy)   C02 = Sxy Sy - Syy Sx
+ *                       C11 = Sxx n - Sx^2   C12 = -(Sxx Sy - Sxy Sx)   C22 = Sxx Syy - Sxy^2     D = Sxx C00 + Sxy C01 + Sx C02
+ *   n < min_pts or D == 0 (collinear support): slot 1, zeros.
+ *   a = ((C00 Tx + C01 Ty) + C02 Tw) / D    b = ((C01 Tx + C11 Ty) + C12 Tw) / D    c = ((C02 Tx + C12 Ty) + C22 Tw) / D
+ *     (the integers converted to double, exactly);   w_f = w_c + c;   c0 = (w_f - a x) - b y
+ *   g_i = (K[0][i] a + K[1][i] b) + K[2][i] c0      len = sqrt((g0^2 + g1^2) + g2^2)
+ *   ray_i = (Kinv[i][0] x + Kinv[i][1] y) + Kinv[i][2]      rl = sqrt((ray0^2 + ray1^2) + ray2^2)
+ *   !(w_f > 0), len not finite or len == 0: slot 2, zeros.
+ *   Otherwise slot 3:  n_cam = -g / len (it faces the camera: g . X_c = w_f d_c > 0),  N_i = (R[0][i] n0 + R[1][i] n1) + R[2][i] n2,
+ *     cos = w_f / (len * rl);  the four values are rounded once to fp32.
+ * One workgroup per image tile with its halo staged once in LDS as fp64 w (0 = not usable), one lane per pixel, one 16-byte store per
+ * pixel, LDS slot counters and one u64 integer atomic per non-zero slot per workgroup: every output is bitwise independent of the tile
+ * shape and of the launch order.  B = 0, H = 0 or W = 0: nothing is touched.
+ * DMVS_EINVAL (before any launch): B, H or W < 0, H W >= 2^31 or B H W > 2^40, NULL depth / cams / out / counts with work to do, radius
+ * outside 1 .. DMVS_NORMAL_MAX_RADIUS, min_pts outside 3 .. (2 radius + 1)^2, rel_jump negative or not finite, a non-finite cams entry,
+ * depth not 4-byte, out not 16-byte or counts not 8-byte aligned. */
+#define DMVS_NORMAL_MAX_RADIUS 4
+#define DMVS_NORMAL_CAM_DOUBLES 27
+#define DMVS_NORMAL_VIEW_CHUNK 8
+#define DMVS_NORMAL_SLOTS 4
+int dmvs_depth_normals_f32(const float* depth, const uint8_t* valid, const double* cams, int64_t B, int32_t H, int32_t W,
+                           int32_t radius, double rel_jump, int32_t min_pts, float* out, int64_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
