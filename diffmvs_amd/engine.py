@@ -55,13 +55,28 @@ def pack_feature(sd, p="feature", g4=False, feat_dtype=torch.float32):
     return f
 
 
+# On: 1.12 against 0.69 + 0.58 ms per 96-image launch (profiles/stem3_kernel_stats_*.csv); the step 0.5-1.2 ms shorter in three interleaved
+# sessions, in one of them every fused run ahead of every other run (profiles/stem3_step_ab.json); DMVS_STEM_FUSE=0 turns it off
+STEM_FUSE_DEFAULT = "1"
+
+
+def stem3_applies(o: Ops, x):
+    """conv1.0 runs inside the stem kernel (Ops.featurenet_stem3) under conv_arith = "split" -- the kernel computes conv0.1 and conv1.0 in split
+    arithmetic only -- wherever its geometry applies; DMVS_STEM_FUSE=0 is the A/B knob: the stem and conv1.0 as two launches"""
+    return (o.conv_arith == K.ARITH_SPLIT and os.environ.get("DMVS_STEM_FUSE", STEM_FUSE_DEFAULT) != "0" and
+            o.featurenet_stem3_supported(x))
+
+
 def run_feature(o: Ops, f, x, layout=K.LAYOUT_NHWC, feat_dtype=torch.float32):
     """x [N,3,H,W] -> {'stage1': [N,H/8,W/8,48], 'stage2': [N,H/4,W/4,32], ('stage3': [N,H/2,W/2,16])} (NHWC by
     default: the layout the warp kernels read; feat_dtype bf16 / fp16 = reduced-precision feature storage, rounded in the
     output convolutions' epilogue)."""
     R = K.ACT_RELU
-    c0 = o.featurenet_stem(f["conv0.0"], f["conv0.1"], x)      # conv0.0 + conv0.1 fused: the 8-channel intermediate stays in LDS
-    c1 = o.conv2d(f["conv1.0"], c0, act=R)
+    if stem3_applies(o, x):
+        c1 = o.featurenet_stem3(f["conv0.0"], f["conv0.1"], f["conv1.0"], x)      # conv0.0 + conv0.1 + conv1.0: c0 has no other reader, it stays in LDS
+    else:
+        c0 = o.featurenet_stem(f["conv0.0"], f["conv0.1"], x)      # conv0.0 + conv0.1 fused: the 8-channel intermediate stays in LDS
+        c1 = o.conv2d(f["conv1.0"], c0, act=R)
     c1 = o.conv2d(f["conv1.2"], o.conv2d(f["conv1.1"], c1, act=R), act=R)
     c2 = o.conv2d(f["conv2.2"], o.conv2d(f["conv2.1"], o.conv2d(f["conv2.0"], c1, act=R), act=R), act=R)
     c3 = o.conv2d(f["conv3.2"], o.conv2d(f["conv3.1"], o.conv2d(f["conv3.0"], c2, act=R), act=R), act=R)

@@ -382,6 +382,34 @@ class Ops:
         self._call("dmvs_featurenet_stem_f32", _ptr(x), _ptr(pc0.weight), _ptr(pc0.scale), _ptr(pc0.shift), _ptr(pc1.weight),
                    _ptr(pc1.scale), _ptr(pc1.shift), _ptr(y), N, H, W, tune, self.stream())
 
+    @staticmethod
+    def featurenet_stem3_supported(x):
+        """geometry of dmvs_featurenet_stem3_f32: even H, rows of whole 16-byte pieces on 16-byte aligned tensors"""
+        xs = x if isinstance(x, (list, tuple)) else [x]
+        H, W = xs[0].shape[2], xs[0].shape[3]
+        return H % 2 == 0 and W % 4 == 0 and 3 * H * W < 2 ** 31 and all(t.data_ptr() % 16 == 0 for t in xs)
+
+    def featurenet_stem3(self, pc0: PackedConv, pc1: PackedConv, pc2: PackedConv, x, tune=None):
+        """relu(bn(conv1.0(relu(bn(conv0.1(relu(bn(conv0.0(x))))))))) of FeatureNet in one kernel: x [N,3,H,W] -> [N,16,H/2,W/2]; conv0.1 and
+        conv1.0 in split-bf16 arithmetic.  x may be a LIST of V tensors [B,3,H,W] like featurenet_stem's: one launch per view into consecutive
+        slices of one [V*B,16,H/2,W/2] output"""
+        xs = x if isinstance(x, (list, tuple)) else [x]
+        self._chk(*xs)
+        Bv, cin, H, W = xs[0].shape
+        if not (cin == 3 and pc0.cin == 3 and pc0.cout == 8 and pc1.cin == 8 and pc1.cout == 8 and pc0.k == (3, 3) and
+                pc1.k == (3, 3) and pc0.stride == 1 and pc1.stride == 1 and pc0.pad == (1, 1) and pc1.pad == (1, 1) and
+                pc0.cout_pad == 8 and pc1.cout_pad == 8 and pc2.cin == 8 and pc2.cout == 16 and pc2.cout_pad == 16 and pc2.k == (5, 5) and
+                pc2.stride == 2 and pc2.pad == (2, 2)):
+            raise _lib.DmvsError("featurenet_stem3: expects the 3->8->8 3x3 stem of FeatureNet and its 8->16 5x5 stride-2 conv1.0")
+        if not self.featurenet_stem3_supported(xs) or any(t.shape != xs[0].shape for t in xs):
+            raise _lib.DmvsError(f"featurenet_stem3: needs even H, W % 4 == 0 and 16-byte aligned views of one shape, got {tuple(xs[0].shape)}")
+        y = self.empty(len(xs) * Bv, 16, H // 2, W // 2)
+        for v, xv in enumerate(xs):
+            self._call("dmvs_featurenet_stem3_f32", _ptr(xv), _ptr(pc0.weight), _ptr(pc0.scale), _ptr(pc0.shift), _ptr(pc1.weight),
+                       _ptr(pc1.scale), _ptr(pc1.shift), _ptr(pc2.weight), _ptr(pc2.scale), _ptr(pc2.shift), _ptr(y[v * Bv:(v + 1) * Bv]),
+                       Bv, H, W, 0 if tune is None else tune, self.stream())
+        return y
+
     def conv2d_wgrad(self, pc: PackedConv, x0, grad_out, x1=None, *, mul0=None, in_mode=IN_PLAIN, want_bias=False, tune=None,
                      into_gw=None, into_gb=None):
         """Weight gradient of conv2d(pc, x0, x1, mul0=..., in_mode=...) in torch layout [cout, cin, kh, kw]

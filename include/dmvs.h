@@ -160,6 +160,19 @@ int dmvs_featurenet_stem_f32(const float* x, const float* w0, const float* scale
                              const float* scale1, const float* shift1, float* y, int32_t N, int32_t H, int32_t W, int32_t tune,
                              void* stream);
 
+/* The stem AND conv1.0 in one kernel: relu(bn2(conv5x5 stride 2 (relu(bn1(conv3x3(relu(bn0(conv3x3(x))))))))) with 3 -> 8 -> 8 -> 16 channels,
+ * paddings 1, 1, 2 (models/module.py:364-371 conv0 + conv1[0], applied at :399-400); neither 8-channel full-resolution map leaves LDS (a
+ * workgroup marches down a strip of 32 output columns with three row rings).  Inference only: nothing else reads conv0's output there.
+ *   x [N,3,H,W], y [N,16,H/2,W/2] NCHW;  w0 [3][3][3][8], w1 [8][3][3][8], w2 [8][5][5][16] in the kernel weight layout of dmvs_conv2d_f32;
+ *   scale / shift [8] / [8] / [16] = folded eval BatchNorm (NULL = 1 / 0).
+ * Arithmetic: conv0.0 exact fp32, conv0.1 and conv1.0 DMVS_ARITH_SPLIT (bf16 triples, six partial products, fp32 accuracy) -- the entry point
+ * has no exact-fp32 form: callers that want one launch dmvs_featurenet_stem_f32 + dmvs_conv2d_f32.  Every output depends only on its position
+ * in the image (not on N, the grid or the strip a pixel falls into); launches are bit-reproducible.
+ * DMVS_EINVAL unless H is even, W a multiple of 4, x 16-byte aligned and 3*H*W < 2^31.  tune: reserved, pass 0. */
+int dmvs_featurenet_stem3_f32(const float* x, const float* w0, const float* scale0, const float* shift0, const float* w1,
+                              const float* scale1, const float* shift1, const float* w2, const float* scale2, const float* shift2,
+                              float* y, int32_t N, int32_t H, int32_t W, int32_t tune, void* stream);
+
 /* Weight (and bias) gradient of the convolution described by `d` (its input side: in0 / in1 / mul0 / in_mode / kh /
  * kw / stride / pad / cout / cout_pad / B / Hin / Win / Hout / Wout; epilogue fields are ignored; in0 / in1 / mul0 must be DENSE tensors:
  * DMVS_EINVAL when in0_cstride, gate_cstride or out_mul is set):
