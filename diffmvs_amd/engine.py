@@ -67,6 +67,18 @@ def stem3_applies(o: Ops, x):
             o.featurenet_stem3_supported(x))
 
 
+CONV1_PAIR_DEFAULT = "1"
+
+
+def conv1_pair_applies(o: Ops, c1):
+    """conv1.1 + conv1.2 run as one kernel (Ops.conv1_pair) under conv_arith = "split" -- the kernel computes in split arithmetic only, and
+    gives the two launches' bits -- wherever its geometry applies and the map is at least one strip wide (a narrower map leaves most of a
+    workgroup's statically assigned 16-column groups empty; the two launches' 16 x 16 tiles fit it better); DMVS_CONV1_PAIR=0 is the A/B knob:
+    the two launches"""
+    return (o.conv_arith == K.ARITH_SPLIT and os.environ.get("DMVS_CONV1_PAIR", CONV1_PAIR_DEFAULT) != "0" and
+            o.conv1_pair_supported(c1) and c1.shape[3] >= K.Ops.CONV1_PAIR_STRIP)
+
+
 def run_feature(o: Ops, f, x, layout=K.LAYOUT_NHWC, feat_dtype=torch.float32):
     """x [N,3,H,W] -> {'stage1': [N,H/8,W/8,48], 'stage2': [N,H/4,W/4,32], ('stage3': [N,H/2,W/2,16])} (NHWC by
     default: the layout the warp kernels read; feat_dtype bf16 / fp16 = reduced-precision feature storage, rounded in the
@@ -77,7 +89,10 @@ def run_feature(o: Ops, f, x, layout=K.LAYOUT_NHWC, feat_dtype=torch.float32):
     else:
         c0 = o.featurenet_stem(f["conv0.0"], f["conv0.1"], x)      # conv0.0 + conv0.1 fused: the 8-channel intermediate stays in LDS
         c1 = o.conv2d(f["conv1.0"], c0, act=R)
-    c1 = o.conv2d(f["conv1.2"], o.conv2d(f["conv1.1"], c1, act=R), act=R)
+    if conv1_pair_applies(o, c1):
+        c1 = o.conv1_pair(f["conv1.1"], f["conv1.2"], c1)      # conv1.1 + conv1.2: the map between them has no other reader, it stays in LDS
+    else:
+        c1 = o.conv2d(f["conv1.2"], o.conv2d(f["conv1.1"], c1, act=R), act=R)
     c2 = o.conv2d(f["conv2.2"], o.conv2d(f["conv2.1"], o.conv2d(f["conv2.0"], c1, act=R), act=R), act=R)
     c3 = o.conv2d(f["conv3.2"], o.conv2d(f["conv3.1"], o.conv2d(f["conv3.0"], c2, act=R), act=R), act=R)
     out = {"stage1": o.conv2d(f["out1"], c3, out_layout=layout, out_dtype=feat_dtype)}

@@ -410,6 +410,29 @@ class Ops:
                        Bv, H, W, 0 if tune is None else tune, self.stream())
         return y
 
+    CONV1_PAIR_STRIP, CONV1_PAIR_SEGMENT = 80, 64      # csrc/conv1_pair.hip: a work unit's output columns / rows (US, UR)
+
+    @staticmethod
+    def conv1_pair_supported(x):
+        """geometry of dmvs_featurenet_conv1_pair_f32: 16 channels, rows of whole 16-byte pieces on a 16-byte aligned tensor"""
+        return (x.dim() == 4 and x.shape[1] == 16 and x.shape[3] % 4 == 0 and 16 * x.shape[2] * x.shape[3] < 2 ** 31 and
+                x.data_ptr() % 16 == 0)
+
+    def conv1_pair(self, pc1: PackedConv, pc2: PackedConv, x, tune=0):
+        """relu(bn(conv1.2(relu(bn(conv1.1(x)))))) of FeatureNet in one kernel: x [N,16,H,W] -> [N,16,H,W], both layers in split-bf16
+        arithmetic: the bits of conv2d(pc2, conv2d(pc1, x, act=ACT_RELU), act=ACT_RELU) under ARITH_SPLIT.  tune: 1 .. 65535 forces the grid."""
+        self._chk(x)
+        for pc in (pc1, pc2):
+            if not (pc.cin == 16 and pc.cout == 16 and pc.cout_pad == 16 and pc.k == (3, 3) and pc.stride == 1 and pc.pad == (1, 1)):
+                raise _lib.DmvsError("conv1_pair: expects the two 16->16 3x3 stride-1 layers of FeatureNet's conv1")
+        if not self.conv1_pair_supported(x):
+            raise _lib.DmvsError(f"conv1_pair: needs 16 channels, W % 4 == 0 and a 16-byte aligned tensor, got {tuple(x.shape)}")
+        N, _, H, W = x.shape
+        y = self.empty(N, 16, H, W)
+        self._call("dmvs_featurenet_conv1_pair_f32", _ptr(x), _ptr(split_weights(pc1)), _ptr(pc1.scale), _ptr(pc1.shift),
+                   _ptr(split_weights(pc2)), _ptr(pc2.scale), _ptr(pc2.shift), _ptr(y), N, H, W, tune, self.stream())
+        return y
+
     def conv2d_wgrad(self, pc: PackedConv, x0, grad_out, x1=None, *, mul0=None, in_mode=IN_PLAIN, want_bias=False, tune=None,
                      into_gw=None, into_gb=None):
         """Weight gradient of conv2d(pc, x0, x1, mul0=..., in_mode=...) in torch layout [cout, cin, kh, kw]

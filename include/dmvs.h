@@ -173,6 +173,19 @@ int dmvs_featurenet_stem3_f32(const float* x, const float* w0, const float* scal
                               const float* scale1, const float* shift1, const float* w2, const float* scale2, const float* shift2,
                               float* y, int32_t N, int32_t H, int32_t W, int32_t tune, void* stream);
 
+/* FeatureNet conv1.1 + conv1.2 in one kernel: y = relu(bn2(conv3x3(relu(bn1(conv3x3(x)))))) with 16 -> 16 -> 16 channels, stride 1, padding 1
+ * (models/module.py:368-371 conv1[1], conv1[2]); the 16-channel intermediate never leaves LDS (a workgroup marches down a strip of 80 output
+ * columns with two row rings of bf16 triples; half of its waves run each layer).  Inference only: nothing else reads conv1.1's output there.
+ *   x, y [N,16,H,W] NCHW;  wsplit1 / wsplit2 = the layers' weights as dmvs_conv2d_desc.weight_split lays them out (cout_pad = 16:
+ *   [2 chunks][3 tap groups][3 planes][4][16][8] bf16); scale / shift [16] = folded eval BatchNorm (NULL = 1 / 0).
+ * Arithmetic: DMVS_ARITH_SPLIT in both layers, the same matrix instructions on the same operands in the same order as two dmvs_conv2d_f32
+ * launches with arith = DMVS_ARITH_SPLIT: the same bits.  Every output depends only on its position in the image (not on N, the grid or the
+ * unit a pixel falls into).  DMVS_EINVAL unless W is a multiple of 4, x / y / the weights are 16-byte aligned and 16*H*W < 2^31.
+ * tune: 0 = the grid of the occupancy query; 1 .. 65535 = that many workgroups (tests). */
+int dmvs_featurenet_conv1_pair_f32(const float* x, const void* wsplit1, const float* scale1, const float* shift1, const void* wsplit2,
+                                   const float* scale2, const float* shift2, float* y, int32_t N, int32_t H, int32_t W, int32_t tune,
+                                   void* stream);
+
 /* Weight (and bias) gradient of the convolution described by `d` (its input side: in0 / in1 / mul0 / in_mode / kh /
  * kw / stride / pad / cout / cout_pad / B / Hin / Win / Hout / Wout; epilogue fields are ignored; in0 / in1 / mul0 must be DENSE tensors:
  * DMVS_EINVAL when in0_cstride, gate_cstride or out_mul is set):

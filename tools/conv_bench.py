@@ -79,6 +79,33 @@ def main():
     g = torch.Generator(device="cuda").manual_seed(0)
     only = os.environ.get("CONV_ONLY")
     arith = K.CONV_ARITH[os.environ.get("CONV_ARITH", "fp32")]      # CONV_ARITH=fp32|bf16|split
+    pair_row = "feat conv1.1 + conv1.2 pair N576"
+    if not only or ("pair" in only and only in pair_row):
+        # conv1.1 + conv1.2 of the 576-image headline step: the one-kernel pair (Ops.conv1_pair) against the two split launches it replaces,
+        # alternating rounds in one process, median per form
+        so = o.with_conv_arith(K.ARITH_SPLIT)
+        x = torch.randn(576, 16, 256, 320, generator=g, device="cuda")
+        pcs = [K.pack_conv2d(torch.randn(16, 16, 3, 3, generator=g, device="cuda") * 0.1, None, stride=1, pad=(1, 1)) for _ in range(2)]
+        forms = [lambda: so.conv1_pair(pcs[0], pcs[1], x), lambda: so.conv2d(pcs[1], so.conv2d(pcs[0], x, act=K.ACT_RELU), act=K.ACT_RELU)]
+        equal = bool(torch.equal(forms[0](), forms[1]()))
+        times = [[], []]
+        for _ in range(5):
+            for f, ts in zip(forms, times):
+                f()
+                st, en = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                st.record()
+                for _ in range(5):
+                    f()
+                en.record()
+                torch.cuda.synchronize()
+                ts.append(st.elapsed_time(en) * 200.0)
+        us_pair, us_two = sorted(times[0])[2], sorted(times[1])[2]
+        print(json.dumps({"layer": pair_row, "us_pair": round(us_pair, 1), "us_two_launches": round(us_two, 1),
+                          "ratio": round(us_pair / us_two, 4), "equal": equal, "pair_runs": [round(t, 1) for t in times[0]],
+                          "two_runs": [round(t, 1) for t in times[1]]}), flush=True)
+        del x
+        if only:
+            return
     for name, N, cin, cout, k, s, H, W in SHAPES:
         if only and only not in name:
             continue
