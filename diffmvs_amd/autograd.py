@@ -24,6 +24,20 @@ def _packed(cache, key, pins, make):
     return hit[0]
 
 
+def _crop(g, spatial):
+    """the leading `spatial` extent of g's trailing dims.  The adjoint of a stride-2 layer (zero-insert conv, transposed conv) is as long
+    as the LONGEST input that gives this output: 2*out + k - 1 - 2*pad, up to stride - 1 more than the input that was convolved; the forward
+    never read those trailing rows / columns, so they are no part of the gradient.  Never shorter; the tensor itself when nothing is cut
+    (every layer of the model: even sizes)."""
+    n = len(spatial)
+    have = tuple(g.shape[-n:])
+    spatial = tuple(spatial)
+    assert all(h >= s for h, s in zip(have, spatial)), f"input gradient {have} shorter than the input {spatial}"
+    if have == spatial:
+        return g
+    return g[(...,) + tuple(slice(0, s) for s in spatial)].contiguous()
+
+
 class _Conv2dFn(torch.autograd.Function):
     """conv2d(x, weight, bias) with stride 1|2 and the fused input modes of the forward kernel."""
 
@@ -56,6 +70,8 @@ class _Conv2dFn(torch.autograd.Function):
                 return pack_conv2d(wb, None, stride=1, pad=(kh - 1 - pc.pad[0], kw - 1 - pc.pad[1]))
             pcb = _packed(ctx.cache, ("bwd", id(weight), pc.pad), (weight,), flipped)
             gl = ops.conv2d(pcb, g, in_mode=(K.IN_ZEROINSERT2 if pc.stride == 2 else K.IN_PLAIN))
+            H, W = x.shape[2], x.shape[3]
+            gl = _crop(gl, (2 * H, 2 * W) if in_mode == K.IN_UPSAMPLE2 else ((H // 2, W // 2) if in_mode == K.IN_UNSHUFFLE2 else (H, W)))
             if in_mode == K.IN_UPSAMPLE2:
                 gx = F.avg_pool2d(gl, 2) * 4.0          # adjoint of nearest x2
             elif in_mode == K.IN_UNSHUFFLE2:
@@ -107,9 +123,10 @@ class _Conv3dFn(torch.autograd.Function):
             if transposed:      # adjoint of the transposed conv = the stride-2 conv with the same weight tensor
                 gx = ops.conv3d(pack_conv3d(w, stride=2), g)
             elif stride == 2:   # adjoint of the stride-2 conv = the transposed conv with the same weight tensor
-                gx = ops.conv3d(pack_conv3d(w, stride=2, transposed=True), g)
+                gx = ops.conv3d(pack_conv3d(w, stride=2, transposed=True), g)      # always 2 * Dout long: one more than an odd input
             else:
                 gx = ops.conv3d(pack_conv3d(w.flip(2, 3, 4).permute(1, 0, 2, 3, 4).contiguous()), g)
+            gx = _crop(gx, x.shape[2:])
         want_b = ctx.has_bias and ctx.needs_input_grad[2]
         if ctx.needs_input_grad[1]:
             if transposed:      # roles swapped: "input" = grad_out, "output gradient" = x; result is [cin_t, cout_t, 3,3,3]

@@ -1271,7 +1271,10 @@ def test_view_aggregate_backward(ops):
     (5, 16, 7, 1, 3, "plain"), (8, 8, 3, 1, 1, "upsample"), (4, 12, 1, 1, 0, "unshuffle"), (9, 7, (1, 5), 1, (0, 2), "plain"),
 ])
 def test_conv2d_autograd(ops, cin, cout, k, stride, pad, in_mode):
-    """forward / input gradient / weight gradient / bias gradient of the training conv against F.conv2d's autograd"""
+    """forward / input gradient / weight gradient / bias gradient of the training conv against F.conv2d's autograd: every kernel family and
+    input mode once, in ONE spatial tile (12 x 20), one n-tile and at most two channel chunks, at fp32-ATen tolerances.  Several tiles, the
+    NT = 2..4 and two-group forms of the zero-insert kernel, odd sizes, the 5x1 kernel and fp64 references: test_conv2d_input_grad_exact /
+    _precision / _step_cache at the end of this file"""
     from diffmvs_amd import autograd as A
     B, H, W = 2, 12, 20
     ks = (k, k) if isinstance(k, int) else k
@@ -1318,6 +1321,9 @@ def test_conv2d_wgrad_refuses_channel_slices(ops):
 @pytest.mark.parametrize("cin,cout,stride,transposed", [(4, 8, 1, False), (8, 16, 2, False), (16, 8, 2, True), (8, 1, 1, False),
                                                          (20, 12, 1, False)])
 def test_conv3d_autograd(ops, cin, cout, stride, transposed):
+    """forward and the three gradients of the training conv3d against ATen's fp32 autograd in a 6 x 8 x 10 volume (transposed: 3 x 4 x 5):
+    at most two tiles per axis, and the stride-1 dgrads run the generic kernel.  The paired streaming kernels (>= 512 tiles), two n-tiles,
+    several tiles of the stride-2 <-> transposed adjoints, odd sizes and fp64 references: test_conv3d_input_grad_exact / _precision"""
     from diffmvs_amd import autograd as A
     B, D, H, W = 2, 6, 8, 10
     if transposed:
@@ -2276,3 +2282,374 @@ def test_conv3d_wgrad_walking_tiles_precision(ops, case):
     _assert_precision(f"conv3d wgrad {case.name} gw", ops.device, gw, d["ref32"][0], d["ref64"][0])
     if case.bias:
         _assert_precision(f"conv3d wgrad {case.name} gb", ops.device, gb, d["ref32"][1], d["ref64"][1])
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# The input-gradient ("dgrad") paths of diffmvs_amd/autograd.py past one tile.  _Conv2dFn.backward gets dX from the FORWARD kernel on
+# flipped, cin <-> cout transposed weights with pad' = k - 1 - pad: directly for the stride-1 layers, through the zero-insert input mode
+# IN_ZEROINSERT2 for the stride-2 ones.  The zero-insert mode is the `ZI = true` instantiation of conv2d_mfma_kernel (its own parity
+# predicate in the staging map, always the 16 x 8 tile, 4-byte staging pieces, always the padding pass) and NOTHING but A.conv2d's backward
+# reaches it: no forward layer, no engine path, no other test.  _Conv3dFn.backward uses the stride-2 <-> transposed adjoint pair and
+# flipped stride-1 weights through dmvs_conv3d_f32.  test_conv2d_autograd / test_conv3d_autograd run all of that in ONE spatial tile
+# with one n-tile and <= 2 channel chunks, at close(1e-4) against fp32 ATen -- a dropped halo column or a wrong parity on one tile border
+# is a small fraction of a sum of cout * k^2 terms and hides there.  The rows below each ASSERT, from their shape alone, the dispatch
+# property they exist for (the rule of launch_conv2d: n-tiles = ceil(cout_pad / 16) of the DGRAD's output channels = the layer's cin;
+# nt = n-tiles if <= 4, else 3 if a multiple of 3, else 4; groups = ceil(n-tiles / nt); channel chunk ConvCfg::CK), so that retuning the
+# dispatch fails them and does not quietly make them one-tile tests.
+#   (NT, groups) of the ZI form per stride-2 layer of the model -- dgrad cin = layer cout, dgrad cout = layer cin:
+#     FeatureNet conv1.0  8 -> 16 5x5 (1, 1), 2 chunks      ContextNet layer1.0.conv1 / .downsample  8 -> 16 3x3 (1, 1), 2 chunks
+#     FeatureNet conv2.0 16 -> 32 5x5 (1, 1), 4 chunks      ContextNet layer2.0.conv1 / .downsample 16 -> 32 3x3 (1, 1), 4 chunks
+#     FeatureNet conv3.0 32 -> 64 5x5 (2, 1), 16 chunks     ContextNet layer3.0.conv1 / .downsample 32 -> 48 3x3 (2, 1), 6 chunks
+#     hidden_init.0.0 / .1.1 32 -> 32 3x3 (2, 1), 4 chunks  hidden_init.1.0 20 -> 32 3x3 (2, 1), 4 chunks
+#   The NT = 3, 4 instantiations and a second n-group (blockIdx.y > 0) are compiled and reachable (any layer with > 32 input channels and
+#   stride 2) but no model layer uses them; the rows zi33_nt3 / zi33_nt4 / zi33_two_groups / zi55_groups3 are their only coverage.
+#   exact:     x, w, b and the output gradient drawn from {-2..2}: every product and partial sum is an integer far below 2^24, so fp32 is
+#              exact in ANY summation order and the output, x.grad, w.grad and b.grad must EQUAL ATen's fp64 autograd on the CPU.
+#   precision: uniform inputs; x.grad's error against the fp64 gradient may be 8 x that of ATen's own fp32 CPU gradient (as for the weight
+#              gradient above: one fp32 MFMA chain of up to cout * k^2 terms per output against ATen's blocked sums).
+# H, W: the STORED size of x (UPSAMPLE2: half, UNSHUFFLE2: twice the convolution's input); cin: stored channels of x.
+# Measured x.grad precision -- kernel error vs fp64 (the same on the emulation and on the MI355X: same products, same order), then ATen's
+# fp32 error vs fp64 = the yardstick with (kernel error / yardstick; must be <= 8), first where the CPU suite ran, second on the MI355X's
+# host (ATen's blocking follows the host's thread count).  Dispatch of the zero-insert rows: nt x groups, chunks x channels, tiles y x x:
+#   case               nt x g  chunks  tiles      | gx kernel: yardstick (ratio) CPU suite, MI355X host
+#   zi33_nt1_chunks     1 x 1   3 x 8   5 x 3 x B2 | 2.7e-07: 2.0e-07 (1.38), 2.0e-07 (1.38)
+#   zi33_nt2            2 x 1   6 x 8   5 x 3 x B2 | 6.0e-07: 3.1e-07 (1.94), 3.1e-07 (1.94)
+#   zi33_nt3            3 x 1   2 x 8   5 x 3      | 2.5e-07: 1.9e-07 (1.29), 1.9e-07 (1.29)
+#   zi33_nt4            4 x 1   4 x 4   3 x 3      | 2.6e-07: 2.3e-07 (1.16), 2.3e-07 (1.16)
+#   zi33_two_groups     4 x 2   3 x 4   3 x 3      | 2.3e-07: 2.5e-07 (0.95), 1.5e-07 (1.61)
+#   zi55_groups3        3 x 2   2 x 4   3 x 3      | 3.5e-07: 1.5e-07 (2.30), 1.5e-07 (2.30)
+#   zi55_conv1_0        1 x 1   2 x 8   5 x 3 x B2 | 3.8e-07: 1.6e-07 (2.36), 1.6e-07 (2.36)
+#   zi55_conv3_0        2 x 1  16 x 4   5 x 3      | 7.5e-07: 3.9e-07 (1.93), 3.9e-07 (1.93)
+#   zi_cin1             1 x 1   1 x 8   5 x 3      | 1.9e-07: 7.7e-08 (2.44), 7.7e-08 (2.44)
+#   flip_pad0                                     | 2.7e-07: 1.2e-07 (2.35), 1.2e-07 (2.35)
+#   flip_k51                                      | 2.4e-07: 2.1e-07 (1.17), 2.1e-07 (1.17)
+#   flip_k77                                      | 1.0e-06: 6.0e-07 (1.71), 6.0e-07 (1.71)
+#   flip_k11_cin1                                 | 2.0e-07: 2.0e-07 (1.00), 2.0e-07 (1.00)
+#   flip_k11_cout1                                | 3.0e-08: 3.0e-08 (1.00), 3.0e-08 (1.00)
+#   upsample_tiles                                | 2.8e-07: 2.2e-07 (1.27), 2.2e-07 (1.27)
+#   unshuffle_tiles                               | 9.5e-08: 9.5e-08 (1.00), 9.5e-08 (1.00)
+# On the MI355X the 21 exact, 16 precision, 2 cache and 4 refusal rows together with the 3-D rows below run in under 4 s.
+_G2 = collections.namedtuple("_G2", "name cin cout k stride pad mode B H W nt groups props")
+_IGRAD2D = [
+    # the zero-insert form (stride 2)
+    _G2("zi33_nt1_chunks", 8, 20, (3, 3), 2, (1, 1), "plain", 2, 36, 44, 1, 1, ("chunks", "partial", "tiles", "ragged", "batch")),
+    _G2("zi33_nt2", 32, 48, (3, 3), 2, (1, 1), "plain", 2, 36, 44, 2, 1, ("chunks", "tiles", "ragged", "batch")),        # ContextNet layer3.0
+    _G2("zi33_nt3", 40, 12, (3, 3), 2, (1, 1), "plain", 1, 36, 44, 3, 1, ("chunks", "partial", "tiles", "ragged")),
+    _G2("zi33_nt4", 64, 16, (3, 3), 2, (1, 1), "plain", 1, 20, 36, 4, 1, ("chunks", "tiles", "ragged")),
+    _G2("zi33_two_groups", 72, 12, (3, 3), 2, (1, 1), "plain", 1, 20, 36, 4, 2, ("chunks", "live1", "tiles", "ragged")),     # 5 n-tiles
+    _G2("zi55_groups3", 96, 8, (5, 5), 2, (2, 2), "plain", 1, 20, 36, 3, 2, ("chunks", "tiles", "ragged")),                  # 6 n-tiles
+    _G2("zi55_conv1_0", 8, 16, (5, 5), 2, (2, 2), "plain", 2, 36, 44, 1, 1, ("chunks", "tiles", "ragged", "batch")),      # FeatureNet conv1.0
+    _G2("zi55_conv3_0", 32, 64, (5, 5), 2, (2, 2), "plain", 1, 36, 44, 2, 1, ("chunks", "tiles", "ragged")),              # FeatureNet conv3.0
+    _G2("zi_cin1", 1, 8, (3, 3), 2, (1, 1), "plain", 1, 36, 44, 1, 1, ("tiles", "ragged")),                                # dgrad with ONE output channel
+    # odd sizes: the dgrad comes out one row / column longer than x and is cropped; `dead`: x's last row or column is read by no window
+    _G2("zi_odd_k33", 16, 8, (3, 3), 2, (1, 1), "plain", 2, 13, 21, 1, 1, ("crop_h", "crop_w", "batch")),
+    _G2("zi_odd_k55", 6, 10, (5, 5), 2, (2, 2), "plain", 1, 13, 21, 1, 1, ("crop_h", "crop_w")),
+    _G2("zi_odd_pad0_h", 16, 8, (3, 3), 2, (0, 0), "plain", 1, 13, 22, 1, 1, ("crop_h", "dead_w")),
+    _G2("zi_odd_pad0_w", 16, 8, (3, 3), 2, (0, 0), "plain", 1, 14, 21, 1, 1, ("crop_w", "dead_h")),
+    _G2("zi_odd_k55_pad1", 8, 8, (5, 5), 2, (1, 1), "plain", 1, 20, 21, 1, 1, ("crop_w",)),
+    # flipped weights (stride 1)
+    _G2("flip_pad0", 8, 8, (3, 3), 1, (0, 0), "plain", 1, 20, 36, 1, 1, ("tiles", "ragged", "grows")),       # pad' = 2: "full" padding, output larger than input
+    _G2("flip_k51", 9, 7, (5, 1), 1, (2, 0), "plain", 2, 20, 36, 1, 1, ("tiles", "ragged", "batch")),        # the 5x1 GRU layer (1x5: test_conv2d_autograd)
+    _G2("flip_k77", 12, 24, (7, 7), 1, (3, 3), "plain", 1, 20, 20, 1, 1, ("tiles", "ragged")),               # the init conv
+    _G2("flip_k11_cin1", 1, 32, (1, 1), 1, (0, 0), "plain", 2, 9, 13, 1, 1, ("batch",)),                     # dgrad cout = 1 (`conf` / final_conv heads)
+    _G2("flip_k11_cout1", 32, 1, (1, 1), 1, (0, 0), "plain", 2, 9, 13, 2, 1, ("batch",)),                    # dgrad cin = 1
+    # adjoints of the fused input modes over several tiles
+    _G2("upsample_tiles", 8, 8, (3, 3), 1, (1, 1), "upsample", 1, 20, 36, 1, 1, ("tiles",)),                 # dgrad 40 x 72, then avg_pool2d * 4
+    _G2("unshuffle_tiles", 4, 12, (1, 1), 1, (0, 0), "unshuffle", 1, 40, 72, 1, 1, ("tiles", "ragged")),     # dgrad 16 ch 20 x 36, then pixel_shuffle
+]
+_IGRAD2D_IDS = [c.name for c in _IGRAD2D]
+_IGRAD2D_NO_DUPLICATES = [c for c in _IGRAD2D if not c.name.startswith("zi_odd")]      # the precision rows: the odd sizes run the same kernels
+
+
+def _pad16mod32(n):
+    """smallest m >= n with m % 32 == 16 (csrc/conv2d_tiled.h)"""
+    return n + (16 - n) % 32
+
+
+def _zi_chunk(k, nt):
+    """ConvCfg<KH, KW, 1, NT, MT = 2>::CK of the fp32 form, the only one the zero-insert mode runs: 16 x 8 output pixels, halo tile
+    (7 + kh) x (15 + kw), 8 channels per chunk unless the double buffer of halo + weight slab would exceed 40 KB"""
+    plane, wpad = _pad16mod32((7 + k[0]) * (15 + k[1])), _pad16mod32(k[0] * k[1] * nt * 16)
+    return 4 if 2 * 8 * (plane + wpad) * 4 > 40960 else 8
+
+
+def _igrad2d_geometry(c):
+    """channels and (H, W) of the convolution's logical input, its output size, and the size of the dgrad as the kernel produces it
+    (stride 2: 2 * out + k - 1 - 2 * pad, the longest input with that output)"""
+    if c.mode == "upsample":
+        cin, Hin, Win = c.cin, 2 * c.H, 2 * c.W
+    elif c.mode == "unshuffle":
+        cin, Hin, Win = 4 * c.cin, c.H // 2, c.W // 2
+    else:
+        cin, Hin, Win = c.cin, c.H, c.W
+    out = tuple((n + 2 * p - k) // c.stride + 1 for n, p, k in zip((Hin, Win), c.pad, c.k))
+    dg = tuple(c.stride * o + k - 1 - 2 * p for o, k, p in zip(out, c.k, c.pad))
+    return cin, (Hin, Win), out, dg
+
+
+def _igrad2d_assert_dispatch(c):
+    """the properties a row exists for, from its shape alone"""
+    cin, (Hin, Win), (Hout, Wout), (Hg, Wg) = _igrad2d_geometry(c)
+    known = {"chunks", "partial", "live1", "tiles", "ragged", "batch", "crop_h", "crop_w", "dead_h", "dead_w", "grows"}
+    assert set(c.props) <= known, c.props
+    ntiles = -(-K._pad_cout(cin) // 16)                      # the dgrad's output channels are the layer's input channels
+    nt = ntiles if ntiles <= 4 else (3 if ntiles % 3 == 0 else 4)
+    groups = -(-ntiles // nt)
+    assert (nt, groups) == (c.nt, c.groups), f"{c.name}: dgrad runs nt {nt} x {groups} groups, the row is for {c.nt} x {c.groups}"
+    zi = c.stride == 2
+    if zi:
+        assert c.k in ((3, 3), (5, 5)) and c.mode == "plain"
+        ck = _zi_chunk(c.k, nt)
+        tile_w, tile_h = 16, 8
+    else:
+        ck = None                                            # (the chunk properties are the zero-insert rows')
+        # widest / tallest tile any stride-1 form could take: 32 columns (3x3 / 5x5 two-wave-wide tiles), 16 rows, 32 where 3x3 tall tiles apply
+        tile_w, tile_h = (32 if c.k[0] * c.k[1] in (9, 25) else 16), (32 if c.k == (3, 3) and Hg >= 32 else 16)
+    if "chunks" in c.props:
+        assert zi and c.cout > ck, f"{c.name}: {c.cout} dgrad input channels are one chunk of {ck}"
+    if "partial" in c.props:
+        assert zi and c.cout % ck, f"{c.name}: {c.cout} dgrad input channels are whole chunks of {ck}"
+    if "live1" in c.props:
+        assert groups == 2 and ntiles - nt == 1
+    if "tiles" in c.props:
+        assert Wg > tile_w and Hg > tile_h, f"{c.name}: dgrad {Hg} x {Wg} is one {tile_h} x {tile_w} tile in an axis"
+    if "ragged" in c.props:
+        assert Wg % 16 and Hg % 8 and (zi or Hg % 16), f"{c.name}: dgrad {Hg} x {Wg} has no ragged last tile"
+    if "batch" in c.props:
+        assert c.B > 1
+    for ax, (n, g) in enumerate(((Hin, Hg), (Win, Wg))):
+        assert g >= n
+        assert (g == n + 1) == ("crop_" + "hw"[ax] in c.props), f"{c.name}: axis {ax} dgrad {g} for an input of {n}"
+        last_read = (((Hout, Wout)[ax] - 1) * c.stride - c.pad[ax] + c.k[ax] - 1)
+        assert (last_read < n - 1) == ("dead_" + "hw"[ax] in c.props), f"{c.name}: axis {ax} last row read {last_read} of {n}"
+    if "grows" in c.props:
+        assert Hg > Hout and Wg > Wout
+
+
+@functools.lru_cache(maxsize=None)
+def _igrad2d_data(c, exact):
+    """inputs of a row and its reference (output, x.grad, w.grad, b.grad), computed once for both backends and left alone: ATen's autograd
+    on the CPU in fp64 (and, for the precision rows, in fp32: the yardstick)"""
+    draw = _ints if exact else rnd
+    cin, _, (Hout, Wout), _ = _igrad2d_geometry(c)
+    x = draw(c.B, c.cin, c.H, c.W, seed=1)
+    w = draw(c.cout, cin, *c.k, seed=2)
+    b = draw(c.cout, seed=3)
+    g = draw(c.B, c.cout, Hout, Wout, seed=4)
+
+    def grads(dt):
+        xr, wr, br = (t.to(dt).clone().requires_grad_(True) for t in (x, w, b))
+        a = xr
+        if c.mode == "upsample":
+            a = F.interpolate(a, scale_factor=2, mode="nearest")
+        elif c.mode == "unshuffle":
+            a = O._pixel_unshuffle(a)
+        out = F.conv2d(a, wr, br, c.stride, c.pad)
+        out.backward(g.to(dt))
+        return out.detach(), xr.grad, wr.grad, br.grad
+    return dict(x=x, w=w, b=b, g=g, ref64=grads(torch.float64), ref32=None if exact else grads(torch.float32))
+
+
+def _igrad2d_run(ops, c, d, cache=None):
+    """one forward + backward through A.conv2d on FRESH leaves (t.to(float32) would return the same tensor and .grad would accumulate)"""
+    from diffmvs_amd import autograd as A
+    x, w, b = (t.clone().to(ops.device).requires_grad_(True) for t in (d["x"], d["w"], d["b"]))
+    out = A.conv2d(ops, x, w, b, stride=c.stride, pad=c.pad, in_mode=_IN_MODES[c.mode], cache=cache)
+    out.backward(dev(ops, d["g"].clone()))
+    return out.detach(), x.grad, w.grad, b.grad
+
+
+_IGRAD_PARTS = ("output", "x.grad", "w.grad", "b.grad")
+
+
+def _assert_equals_fp64(what, got, ref64):
+    for name, a, r in zip(_IGRAD_PARTS, got, ref64):
+        if r is None:
+            assert a is None, f"{what} {name}"
+            continue
+        assert float(r.abs().max()) < 2 ** 24, f"{what} {name}: the reference leaves the exact range"
+        assert tuple(a.shape) == tuple(r.shape), f"{what} {name}: shape {tuple(a.shape)}, fp64 reference {tuple(r.shape)}"
+        bad = int((a.cpu() != r.float()).sum())
+        assert bad == 0, f"{what} {name} differs from the fp64 result in {bad} of {r.numel()} elements"
+
+
+@pytest.mark.parametrize("case", _IGRAD2D, ids=_IGRAD2D_IDS)
+def test_conv2d_input_grad_exact(ops, case):
+    """A.conv2d forward + backward on integer-valued inputs (block comment above): output, x.grad, w.grad and b.grad EQUAL ATen's fp64
+    autograd, a second backward of a fresh graph gives the same bits, and an input row / column that no window reads gets a zero gradient;
+    the odd-size rows need the crop of _Conv2dFn.backward (without it: `returned an invalid gradient at index 0`)"""
+    _igrad2d_assert_dispatch(case)
+    d = _igrad2d_data(case, True)
+    if "dead_h" in case.props:
+        assert not d["ref64"][1][:, :, -1].any() and d["ref64"][1][:, :, -2].any()
+    if "dead_w" in case.props:
+        assert not d["ref64"][1][..., -1].any() and d["ref64"][1][..., -2].any()
+    got = _igrad2d_run(ops, case, d)
+    _assert_equals_fp64(f"conv2d {case.name}", got, d["ref64"])
+    again = _igrad2d_run(ops, case, d)
+    for name, a, b in zip(_IGRAD_PARTS, got, again):
+        assert torch.equal(a, b), f"conv2d {case.name} {name}: two runs differ"
+
+
+@pytest.mark.parametrize("case", _IGRAD2D_NO_DUPLICATES, ids=[c.name for c in _IGRAD2D_NO_DUPLICATES])
+def test_conv2d_input_grad_precision(ops, case):
+    """the same rows with uniform(-1, 1) inputs: x.grad's error against the fp64 gradient is at most 8 x the error of ATen's own fp32 CPU
+    gradient (both as close() measures them); the figures are printed before they are asserted"""
+    _igrad2d_assert_dispatch(case)
+    d = _igrad2d_data(case, False)
+    gx = _igrad2d_run(ops, case, d)[1]
+    assert tuple(gx.shape) == tuple(d["x"].shape)
+    _assert_precision(f"conv2d dgrad {case.name} gx", ops.device, gx, d["ref32"][1], d["ref64"][1])
+
+
+@pytest.mark.parametrize("direct", [False, True], ids=["autograd_accumulates", "grad_into_bucket"])
+def test_conv2d_input_grad_step_cache(ops, direct):
+    """the per-step cache of A.conv2d: ONE stride-2 weight applied to three inputs in one graph (the update block's three GRU iterations),
+    16 -> 16 3x3 at B2 20 x 36, integers.  All three x.grad and the summed weight / bias gradients EQUAL fp64 -- summed by autograd's
+    AccumulateGrad (cache = {}) or by the fold kernel into integer-valued preallocated .grad tensors (cache["grad_into_bucket"]) -- and
+    the cache ends with exactly one packed forward weight and one flipped backward weight for the tensor"""
+    from diffmvs_amd import autograd as A
+    cin, cout, B, H, W, n = 16, 16, 2, 20, 36, 3
+    xs = [_ints(B, cin, H, W, seed=10 + i) for i in range(n)]
+    gs = [_ints(B, cout, H // 2, W // 2, seed=20 + i) for i in range(n)]
+    w, b = _ints(cout, cin, 3, 3, seed=2), _ints(cout, seed=3)
+    pre_w, pre_b = (_ints(cout, cin, 3, 3, seed=5), _ints(cout, seed=6)) if direct else (torch.zeros_like(w), torch.zeros_like(b))
+    x64 = [t.double().requires_grad_(True) for t in xs]
+    w64, b64 = w.double().requires_grad_(True), b.double().requires_grad_(True)
+    torch.autograd.backward([F.conv2d(t, w64, b64, 2, 1) for t in x64], [t.double() for t in gs])
+    want_w, want_b = pre_w.double() + w64.grad, pre_b.double() + b64.grad
+    assert float(want_w.abs().max()) < 2 ** 24 and float(want_b.abs().max()) < 2 ** 24
+
+    xd = [t.clone().to(ops.device).requires_grad_(True) for t in xs]
+    wd, bd = (t.clone().to(ops.device).requires_grad_(True) for t in (w, b))
+    cache = {}
+    if direct:
+        cache["grad_into_bucket"] = True
+        wd.grad, bd.grad = dev(ops, pre_w.clone(), pre_b.clone())
+        bucket_w, bucket_b = wd.grad, bd.grad
+    outs = [A.conv2d(ops, t, wd, bd, stride=2, pad=1, cache=cache) for t in xd]
+    torch.autograd.backward(outs, [dev(ops, t.clone()) for t in gs])
+    for i in range(n):
+        assert torch.equal(xd[i].grad.cpu(), x64[i].grad.float()), f"x.grad of use {i} differs from the fp64 gradient"
+    assert torch.equal(wd.grad.cpu(), want_w.float()) and torch.equal(bd.grad.cpu(), want_b.float())
+    if direct:      # accumulated in place: autograd got None and did not replace the preallocated tensors
+        assert wd.grad is bucket_w and bd.grad is bucket_b
+    keys = [k for k in cache if isinstance(k, tuple)]
+    assert sorted(k[0] for k in keys) == ["bwd", "fwd"] and all(k[1] == id(wd) for k in keys), keys
+
+
+@pytest.mark.parametrize("k,pad", [((7, 7), (3, 3)), ((1, 1), (0, 0)), ((1, 5), (0, 2)), ((5, 1), (2, 0))])
+def test_conv2d_zero_insert_refuses_other_kernels(ops, k, pad):
+    """the zero-insert input mode exists for the 3x3 and 5x5 kernels only (the model's stride-2 layers): any other kernel is refused with
+    DMVS_EINVAL -- not routed to a form that would read the input as a plain or nearest-x2 one"""
+    pc = K.pack_conv2d(dev(ops, rnd(8, 8, *k, seed=1)), None, stride=1, pad=pad)
+    with pytest.raises(K._lib.DmvsError, match="-22"):
+        ops.conv2d(pc, dev(ops, rnd(1, 8, 6, 8, seed=2)), in_mode=K.IN_ZEROINSERT2)
+
+
+# conv3d: cin / cout of the LAYER, D, H, W of its input; `bias`: the layer has one (the `prob` head; the others are conv + BatchNorm).
+# The dgrad's kernel, from the dispatch of dmvs_conv3d_f32 (asserted per row):
+#   pair / pair8   stride 1, dgrad cin = cout <= 4 / 5..8 and dgrad cout = cin <= 8: the paired streaming kernels (two depth slices per
+#                  MFMA) once ceil(W/16) * ceil(H/4) * ceil(D/8) * B >= 512 -- in a smaller volume (test_conv3d_autograd's, and
+#                  test_conv3d_volumes_smaller_than_a_tile for cin = 1) the generic kernel runs instead
+#   flip2          stride 1, 32 -> 32: the generic kernel with two n-tiles on flipped weights
+#   deconv         stride-2 layer: the matrix-core transposed form over several tiles of the OUTPUT GRADIENT (16 x 4 x 4); `odd`: the dgrad
+#                  comes out 2 * Dout long and is cropped
+#   s2             transposed layer: the stride-2 matrix-core form, one / two n-tiles
+# The three paired rows are 2 x 17 x 57 x 84: 6 * 15 * 3 * 2 = 540 paired tiles, the smallest ragged volume (57 = 14 tiles + 1 row, 84 = 5
+# tiles + 4 columns, a multiple of 4 for the 16-byte halo pieces) above the threshold -- the emulation spends 5-13 s per row on them.
+# Measured x.grad precision, as above (the kernel's error is the same on the emulation and on the MI355X):
+#   case                         | gx kernel: yardstick (ratio) CPU suite, MI355X host
+#   prob_cin1_paired             | 2.2e-07: 2.5e-07 (0.88), 2.5e-07 (0.88)
+#   c4_c8_paired_two_chunks      | 5.8e-07: 5.3e-07 (1.09), 5.3e-07 (1.09)
+#   c8_c8_paired_two_chunks      | 6.0e-07: 5.9e-07 (1.02), 5.9e-07 (1.02)
+#   c32_two_ntiles_flipped       | 1.0e-06: 1.8e-07 (5.46), 1.8e-07 (5.46)      one chain of 32 * 27 = 864 fp32 terms per output
+#   s2_8_16                      | 2.9e-07: 1.0e-07 (2.82), 1.0e-07 (2.82)
+#   s2_16_32                     | 6.4e-07: 1.5e-07 (4.30), 1.5e-07 (4.30)
+#   transposed_32_16             | 8.0e-07: 3.9e-07 (2.06), 3.1e-07 (2.57)
+#   transposed_16_8              | 4.8e-07: 5.7e-07 (0.84), 5.7e-07 (0.84)
+_G3 = collections.namedtuple("_G3", "name cin cout stride transposed B D H W bias kernel")
+_IGRAD3D = [
+    _G3("prob_cin1_paired", 8, 1, 1, False, 2, 17, 57, 84, True, "pair"),          # the `prob` / pixel_view_weight.conv.1 layers: dgrad 1 -> 8
+    _G3("c4_c8_paired_two_chunks", 4, 8, 1, False, 2, 17, 57, 84, False, "pair8"),   # dgrad 8 -> 4: cout 4 under cout_pad 8
+    _G3("c8_c8_paired_two_chunks", 8, 8, 1, False, 2, 17, 57, 84, False, "pair8"),
+    _G3("c32_two_ntiles_flipped", 32, 32, 1, False, 1, 5, 6, 44, False, "flip2"),
+    _G3("s2_8_16", 8, 16, 2, False, 1, 10, 20, 36, False, "deconv"),
+    _G3("s2_16_32", 16, 32, 2, False, 1, 8, 10, 34, False, "deconv"),
+    _G3("s2_8_16_odd", 8, 16, 2, False, 1, 11, 18, 35, False, "deconv_odd"),
+    _G3("s2_16_32_odd", 16, 32, 2, False, 1, 9, 9, 33, False, "deconv_odd"),
+    _G3("transposed_32_16", 32, 16, 2, True, 1, 5, 6, 20, False, "s2_nt2"),
+    _G3("transposed_16_8", 16, 8, 2, True, 2, 5, 10, 18, False, "s2_nt1"),
+]
+_IGRAD3D_IDS = [c.name for c in _IGRAD3D]
+_IGRAD3D_NO_DUPLICATES = [c for c in _IGRAD3D if not c.name.endswith("_odd")]
+
+
+def _igrad3d_out(c):
+    return tuple(2 * n for n in (c.D, c.H, c.W)) if c.transposed else tuple((n - 1) // c.stride + 1 for n in (c.D, c.H, c.W))
+
+
+def _igrad3d_assert_dispatch(c):
+    """the kernel the dgrad of a row takes, from its shape alone: dgrad cin = c.cout, dgrad cout = c.cin"""
+    Do, Ho, Wo = _igrad3d_out(c)
+    ntiles = -(-K._pad_cout(c.cin) // 16)
+    if c.kernel in ("pair", "pair8"):
+        assert c.stride == 1 and not c.transposed and c.cin <= 8 and K._pad_cout(c.cin) == 8
+        assert c.cout <= 4 if c.kernel == "pair" else (4 < c.cout <= 8 and c.W % 4 == 0)      # (pair8: 16-byte halo pieces only)
+        paired = -(-c.W // 16) * -(-c.H // 4) * -(-c.D // 8) * c.B
+        assert paired >= 512, f"{c.name}: {paired} paired tiles: the generic kernel runs below 512"
+    elif c.kernel == "flip2":
+        assert c.stride == 1 and not c.transposed and ntiles == 2
+    elif c.kernel in ("deconv", "deconv_odd"):
+        assert c.stride == 2 and not c.transposed
+        assert -(-Wo // 16) > 1 and -(-Ho // 4) > 1 and -(-Wo // 16) * -(-Ho // 4) * -(-Do // 4) >= 4      # tiles of the transposed form's INPUT
+        assert any(n % 2 for n in (c.D, c.H, c.W)) == (c.kernel == "deconv_odd")
+    else:
+        assert c.transposed and c.stride == 2 and ntiles == {"s2_nt1": 1, "s2_nt2": 2}[c.kernel]
+        assert -(-c.W // 16) > 1 and -(-c.H // 4) > 1 and -(-c.D // 4) > 1                                 # tiles of the dgrad = of x
+
+
+@functools.lru_cache(maxsize=None)
+def _igrad3d_data(c, exact):
+    """inputs and CPU references (output, x.grad, w.grad, b.grad or None) in fp64 (fp32 as well for the precision rows), computed once"""
+    draw = _ints if exact else rnd
+    x = draw(c.B, c.cin, c.D, c.H, c.W, seed=1)
+    w = draw(*((c.cin, c.cout) if c.transposed else (c.cout, c.cin)), 3, 3, 3, seed=2)
+    b = draw(c.cout, seed=3) if c.bias else None
+    g = draw(c.B, c.cout, *_igrad3d_out(c), seed=4)
+
+    def grads(dt):
+        xr, wr = (t.to(dt).clone().requires_grad_(True) for t in (x, w))
+        br = None if b is None else b.to(dt).clone().requires_grad_(True)
+        out = F.conv_transpose3d(xr, wr, br, 2, 1, 1) if c.transposed else F.conv3d(xr, wr, br, c.stride, 1)
+        out.backward(g.to(dt))
+        return out.detach(), xr.grad, wr.grad, None if br is None else br.grad
+    return dict(x=x, w=w, b=b, g=g, ref64=grads(torch.float64), ref32=None if exact else grads(torch.float32))
+
+
+def _igrad3d_run(ops, c, d):
+    from diffmvs_amd import autograd as A
+    x, w = (t.clone().to(ops.device).requires_grad_(True) for t in (d["x"], d["w"]))
+    b = None if d["b"] is None else d["b"].clone().to(ops.device).requires_grad_(True)
+    out = A.conv3d(ops, x, w, b, stride=c.stride, transposed=c.transposed)
+    out.backward(dev(ops, d["g"].clone()))
+    return out.detach(), x.grad, w.grad, None if b is None else b.grad
+
+
+@pytest.mark.parametrize("case", _IGRAD3D, ids=_IGRAD3D_IDS)
+def test_conv3d_input_grad_exact(ops, case):
+    """A.conv3d forward + backward on integer-valued inputs: output, x.grad, w.grad (and b.grad) EQUAL ATen's fp64 autograd; the odd
+    sizes need the crop of _Conv3dFn.backward (the transposed adjoint is always 2 * Dout long)"""
+    _igrad3d_assert_dispatch(case)
+    d = _igrad3d_data(case, True)
+    _assert_equals_fp64(f"conv3d {case.name}", _igrad3d_run(ops, case, d), d["ref64"])
+
+
+@pytest.mark.parametrize("case", _IGRAD3D_NO_DUPLICATES, ids=[c.name for c in _IGRAD3D_NO_DUPLICATES])
+def test_conv3d_input_grad_precision(ops, case):
+    """the same rows with uniform(-1, 1) inputs: x.grad's error against fp64 at most 8 x that of ATen's own fp32 CPU gradient"""
+    _igrad3d_assert_dispatch(case)
+    d = _igrad3d_data(case, False)
+    gx = _igrad3d_run(ops, case, d)[1]
+    assert tuple(gx.shape) == tuple(d["x"].shape)
+    _assert_precision(f"conv3d dgrad {case.name} gx", ops.device, gx, d["ref32"][1], d["ref64"][1])
