@@ -134,6 +134,12 @@ def main(argv=None, device=None):
     ap.add_argument("--normal_min_pts", type=int, default=5, help="--normals: pixels with fewer neighbours in the fit get no normal")
     ap.add_argument("--max_view_angle", type=float, default=None, help="with --filter (implies --normals): leave points out of the cloud that have no normal or "
                     "are seen at more than this many degrees off their normal")
+    ap.add_argument("--mesh", action="store_true", help="with --filter: also write the averaged depth maps (depth_fused/) and mesh every scene to <scene>/mesh.ply "
+                    "(TSDF fusion and surface nets on the GPU: diffmvs_amd.mesh); adds mesh[scene] to the result")
+    ap.add_argument("--mesh_voxel", type=float, default=None, help="--mesh: voxel side in world units")
+    ap.add_argument("--mesh_resolution", type=int, default=512, help="--mesh, without --mesh_voxel: voxels along the longest axis of the scene's box")
+    ap.add_argument("--mesh_trunc", type=float, default=4.0, help="--mesh: truncation distance in voxels")
+    ap.add_argument("--mesh_min_weight", type=int, default=2, help="--mesh: a voxel counts as observed from this many views on")
     ap.add_argument("--gt_ply", default=None, help="with --filter: score every fused cloud against this ground-truth PLY ('{scene}' is substituted) "
                     "with diffmvs_amd.cloud_eval; adds cloud_metrics[scene] to the result")
     ap.add_argument("--gt_transform", default=None, help="--gt_ply: 4x4 text file that moves the fused cloud into the ground truth's frame ('{scene}' is substituted)")
@@ -195,9 +201,16 @@ def main(argv=None, device=None):
             if a.normals or a.max_view_angle is not None:
                 kw.update(normals=True, normal_radius=a.normal_radius, normal_jump=a.normal_jump, normal_min_pts=a.normal_min_pts,
                           max_view_angle=a.max_view_angle, stats=res.setdefault("normals", {}).setdefault(scene, {}))
+            if a.mesh:
+                kw.update(write_fused=True)
             n = fusion.filter_depth(os.path.join(a.testpath, scene), os.path.join(a.outdir, scene), method=a.method, device=device, **kw)
             res.setdefault("fused_points", {})[scene] = n
             res.setdefault("ply", {})[scene] = kw["plyfilename"]
+            if a.mesh:
+                from . import mesh
+                res.setdefault("mesh", {})[scene] = mesh.mesh_scene(
+                    os.path.join(a.outdir, scene), os.path.join(a.testpath, scene), a.dataset, voxel=a.mesh_voxel, resolution=a.mesh_resolution,
+                    trunc=a.mesh_trunc, min_weight=a.mesh_min_weight, device=device)
             if a.gt_ply:
                 from . import cloud_eval, cloud_register
                 extra = {}

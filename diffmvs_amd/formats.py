@@ -301,11 +301,18 @@ def abs_rel_error(depth_est: torch.Tensor, depth_gt: torch.Tensor, mask: torch.T
 
 
 # ------------------------------------------------------------------------------------------ PLY
-def write_ply(filename: str, xyz: np.ndarray, rgb: np.ndarray, normals: np.ndarray | None = None) -> None:
+def write_ply(filename: str, xyz: np.ndarray, rgb: np.ndarray, normals: np.ndarray | None = None, faces: np.ndarray | None = None) -> None:
     """binary little-endian PLY with x y z (float32) red green blue (uint8) per vertex: what plyfile writes for
     filter.py:208-227.  With normals [N,3] the vertex is x y z nx ny nz (float32) red green blue: the property names and the order
-    MeshLab, Open3D and PoissonRecon expect."""
+    MeshLab, Open3D and PoissonRecon expect.  With faces [F,3] (vertex indices) the file also has `element face F` with
+    `property list uchar int vertex_indices`: a triangle mesh.  Without them the bytes are what they were."""
     n = xyz.shape[0]
+    if faces is not None:
+        faces = np.asarray(faces)
+        if faces.ndim != 2 or faces.shape[1] != 3 or faces.dtype.kind not in "iu":
+            raise ValueError(f"write_ply: faces must be an integer [F,3] array, got {faces.dtype} {faces.shape}")
+        if faces.size and (int(faces.min()) < 0 or int(faces.max()) >= n):
+            raise ValueError(f"write_ply: a face names a vertex outside 0 .. {n - 1}")
     if normals is not None and tuple(normals.shape) != (n, 3):
         raise ValueError(f"write_ply: {n} vertices need normals of shape ({n}, 3), got {tuple(normals.shape)}")
     nrm = [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")] if normals is not None else []
@@ -316,9 +323,14 @@ def write_ply(filename: str, xyz: np.ndarray, rgb: np.ndarray, normals: np.ndarr
     v["red"], v["green"], v["blue"] = rgb[:, 0], rgb[:, 1], rgb[:, 2]
     with open(filename, "wb") as f:
         f.write(("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n%s"
-                 "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n"
-                 % (n, "".join("property float %s\n" % k for k, _ in nrm))).encode("ascii"))
+                 "property uchar red\nproperty uchar green\nproperty uchar blue\n%send_header\n"
+                 % (n, "".join("property float %s\n" % k for k, _ in nrm),
+                    "" if faces is None else "element face %d\nproperty list uchar int vertex_indices\n" % faces.shape[0])).encode("ascii"))
         f.write(v.tobytes())
+        if faces is not None:
+            t = np.empty(faces.shape[0], dtype=[("n", "u1"), ("v", "<i4", (3,))])
+            t["n"], t["v"] = 3, faces
+            f.write(t.tobytes())
 
 
 _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2",
@@ -415,3 +427,42 @@ def read_ply(filename: str, with_normals: bool = False):
     if all(k in vertex for k in ("nx", "ny", "nz")):
         normals = np.ascontiguousarray(np.stack([np.asarray(vertex[k], dtype=np.float32) for k in ("nx", "ny", "nz")], -1))
     return np.ascontiguousarray(xyz), rgb, normals
+
+
+def read_ply_mesh(filename: str):
+    """-> (xyz float32 [N,3], rgb uint8 [N,3] or None, faces int32 [F,3]) of a `binary_little_endian` triangle mesh whose vertex element
+    comes first and is followed by a face element with one list property (what write_ply(..., faces=) writes, MeshLab and Open3D too);
+    a file without faces gives [0,3].  The vertices are read_ply's."""
+    xyz, rgb = read_ply(filename)
+    with open(filename, "rb") as f:
+        data = f.read()
+    end = data.find(b"end_header")
+    body = data[data.find(b"\n", end) + 1:]
+    elements = []
+    for line in data[:end].decode("ascii", "replace").splitlines()[1:]:
+        w = line.split()
+        if w and w[0] == "format" and w[1] != "binary_little_endian":
+            raise ValueError(f"{filename}: read_ply_mesh reads binary_little_endian files, not {w[1]!r}")
+        if w and w[0] == "element":
+            elements.append([w[1], int(w[2]), []])
+        elif w and w[0] == "property" and elements:
+            elements[-1][2].append(w[1:])
+    faces = np.zeros((0, 3), np.int32)
+    names = [e[0] for e in elements]
+    if "face" in names:
+        if names[:2] != ["vertex", "face"]:
+            raise ValueError(f"{filename}: expected the vertex element first and the face element next, got {names}")
+        _, count, props = elements[1]
+        if len(props) != 1 or props[0][0] != "list" or props[0][1] not in _PLY_TYPES or props[0][2] not in _PLY_TYPES:
+            raise ValueError(f"{filename}: the face element must have one list property")
+        pos = elements[0][1] * sum(np.dtype(_PLY_TYPES[p[0]]).itemsize for p in elements[0][2])
+        dt = np.dtype([("n", "<" + _PLY_TYPES[props[0][1]]), ("v", "<" + _PLY_TYPES[props[0][2]], (3,))])
+        if pos + count * dt.itemsize > len(body):
+            raise ValueError(f"{filename}: truncated: the header announces {count} faces")
+        rec = np.frombuffer(body, dtype=dt, count=count, offset=pos)
+        if count and not (rec["n"] == 3).all():
+            raise ValueError(f"{filename}: only triangle meshes are supported")
+        faces = np.ascontiguousarray(rec["v"].astype(np.int32))
+        if faces.size and (int(faces.min()) < 0 or int(faces.max()) >= xyz.shape[0]):
+            raise ValueError(f"{filename}: a face names a vertex outside 0 .. {xyz.shape[0] - 1}")
+    return xyz, rgb, faces

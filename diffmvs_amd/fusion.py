@@ -147,7 +147,8 @@ def view_normals(ops: Ops, depth: np.ndarray, mask: np.ndarray, K, E, radius=2, 
 
 def filter_depth(pair_folder, out_folder, plyfilename, geo_mask_thres=3, geo_pixel_thres=1.0, geo_depth_thres=0.01,
                  photo_thres=(0.3, 0.5, 0.5), method="casdiffmvs", dataset="dtu", scan=None, device="cuda:0", ops: Ops | None = None,
-                 normals=False, normal_radius=2, normal_jump=0.02, normal_min_pts=5, max_view_angle=None, stats: dict | None = None) -> int:
+                 normals=False, normal_radius=2, normal_jump=0.02, normal_min_pts=5, max_view_angle=None, stats: dict | None = None,
+                 write_fused=False) -> int:
     """filter.py:95-227 (dataset != 'tank') / :261-441 (dataset == 'tank': `scan` picks the dynamic parameters) over one
     scene's output tree; writes mask/*.png and the fused point cloud.  -> number of fused points.
     normals: the PLY also carries nx ny nz, the oriented normal of every point from view_normals() on the view's averaged depth (fp32)
@@ -155,7 +156,8 @@ def filter_depth(pair_folder, out_folder, plyfilename, geo_mask_thres=3, geo_pix
     without a normal, or seen at more than this angle off their normal (cos < cos(angle)), are left out of the CLOUD; the masks stay
     the reference's.  stats: a dict that receives {"slots": the four slot totals of include/dmvs.h over all views, "no_normal": written
     points that carry (0, 0, 0), "dropped": points max_view_angle left out} when normals are on.  With the defaults every output is
-    what it was without these options."""
+    what it was without these options.
+    write_fused: also writes the averaged depth of every reference view as depth_fused/%08d.pfm (fp32), what diffmvs_amd.mesh integrates."""
     from PIL import Image
     ops = ops or Ops.for_device(device)
     if os.path.dirname(plyfilename):
@@ -176,6 +178,8 @@ def filter_depth(pair_folder, out_folder, plyfilename, geo_mask_thres=3, geo_pix
     verts, cols, nrms = [], [], []
     slots, no_normal, dropped = np.zeros(_lib.NORMAL_SLOTS, np.int64), 0, 0
     os.makedirs(os.path.join(out_folder, "mask"), exist_ok=True)
+    if write_fused:
+        os.makedirs(os.path.join(out_folder, "depth_fused"), exist_ok=True)
     for ref_view, src_views in pairs:
         rd, rk, re_, dmax, dmin = view(ref_view)
         img = IO.read_img(os.path.join(out_folder, f"images/{ref_view:0>8}.jpg"))[0]
@@ -185,6 +189,8 @@ def filter_depth(pair_folder, out_folder, plyfilename, geo_mask_thres=3, geo_pix
                                            geo_depth_thres, method, dynamic)
         for name, m in (("photo", photo), ("geo", geo), ("final", final)):
             Image.fromarray(m.astype(np.uint8) * 255).save(os.path.join(out_folder, f"mask/{ref_view:0>8}_{name}.png"))
+        if write_fused:
+            IO.save_pfm(os.path.join(out_folder, f"depth_fused/{ref_view:0>8}.pfm"), avg.astype(np.float32))
         pts, col = unproject(avg, rk, re_, final), (img[final] * 255).astype(np.uint8)
         if want_normals:
             nrm, cnt = view_normals(ops, avg, final, rk, re_, normal_radius, normal_jump, normal_min_pts)

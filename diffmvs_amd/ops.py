@@ -1024,3 +1024,85 @@ class Ops:
         self._call("dmvs_depth_normals_f32", _ptr(depth), _ptr(valid), cams.ctypes.data_as(C.c_void_p), B, H, W, int(radius), float(rel_jump),
                    int(min_pts), _ptr(out), _ptr(counts), self.stream())
         return out, counts
+
+    # ------------------------------------------------------------------ a surface from depth maps (diffmvs_amd/mesh.py)
+    def tsdf_volume(self, dims, origin, h, colour=True) -> "TsdfVolume":
+        """a zeroed volume of dmvs_tsdf_integrate_f32 (include/dmvs.h): dims (nx, ny, nz), origin (three doubles), voxel side h"""
+        import numpy as np
+        nx, ny, nz = (int(d) for d in dims)
+        if min(nx, ny, nz) < 0 or nx * ny * nz >= 2 ** 31:
+            raise _lib.DmvsError(f"tsdf_volume: dims {(nx, ny, nz)}; the volume must have fewer than 2^31 voxels")
+        origin = np.ascontiguousarray(origin, np.float64).reshape(-1)
+        if origin.shape != (3,) or not np.isfinite(origin).all() or not (float(h) > 0.0 and np.isfinite(h)):
+            raise _lib.DmvsError(f"tsdf_volume: the origin must be three finite numbers and the voxel side positive, got {origin} and {h}")
+        z = lambda *s, dt: torch.zeros(*s, dtype=dt, device=self.device)       # noqa: E731
+        return TsdfVolume((nx, ny, nz), origin, float(h), z(nz, ny, nx, dt=torch.int32), z(nz, ny, nx, dt=torch.int32),
+                          z(nz, ny, nx, 4, dt=torch.int32) if colour else None)
+
+    def _tsdf_vol(self, what, vol):
+        self._chk_typed(what, (vol.S, torch.int32), (vol.Wt, torch.int32), (vol.C, torch.int32))
+        nx, ny, nz = vol.dims
+        if tuple(vol.S.shape) != (nz, ny, nx) or vol.Wt.shape != vol.S.shape or (vol.C is not None and tuple(vol.C.shape) != (nz, ny, nx, 4)):
+            raise _lib.DmvsError(f"{what}: S, Wt (and C) must be [nz,ny,nx](,4) = {(nz, ny, nx)}, got {tuple(vol.S.shape)}, {tuple(vol.Wt.shape)}"
+                                 + (f", {tuple(vol.C.shape)}" if vol.C is not None else ""))
+        return nx, ny, nz, vol.origin.ctypes.data_as(C.c_void_p)
+
+    def tsdf_integrate(self, vol, depth, valid, rgb, views, tau, cull=True):
+        """dmvs_tsdf_integrate_f32 (include/dmvs.h): ADDS the truncated signed distances of V depth maps to the volume.  depth [V,H,W] fp32;
+        valid None or [V,H,W] uint8 / bool; rgb None or [V,H,W,3] uint8 (the volume then needs its colour sums); views [V,12] fp64 on the
+        host (mesh.tsdf_views); tau: the truncation distance.  cull=False: DMVS_TSDF_NO_CULL (the same bits).  -> vol"""
+        import numpy as np
+        if valid is not None and valid.dtype == torch.bool:
+            valid = valid.view(torch.uint8)
+        self._chk_typed("tsdf_integrate", (depth, torch.float32), (valid, torch.uint8), (rgb, torch.uint8))
+        nx, ny, nz, origin = self._tsdf_vol("tsdf_integrate", vol)
+        if depth.dim() != 3 or (valid is not None and valid.shape != depth.shape) or (rgb is not None and tuple(rgb.shape) != tuple(depth.shape) + (3,)):
+            raise _lib.DmvsError(f"tsdf_integrate: depth (and the mask) must be [V,H,W] and rgb [V,H,W,3], got {tuple(depth.shape)}"
+                                 + (f", {tuple(valid.shape)}" if valid is not None else "") + (f", {tuple(rgb.shape)}" if rgb is not None else ""))
+        V, H, W = (int(s) for s in depth.shape)
+        v = np.ascontiguousarray(views.detach().cpu().numpy() if torch.is_tensor(views) else views, dtype=np.float64)
+        if v.shape != (V, _lib.TSDF_VIEW_DOUBLES):
+            raise _lib.DmvsError(f"tsdf_integrate: {V} depth maps need a [{V},{_lib.TSDF_VIEW_DOUBLES}] view table (two rows of P, row 2 of E), got {v.shape}")
+        if rgb is not None and vol.C is None:
+            raise _lib.DmvsError("tsdf_integrate: colours need a volume made with colour=True")
+        if vol.views + V > _lib.TSDF_MAX_VIEWS:
+            raise _lib.DmvsError(f"tsdf_integrate: {vol.views} + {V} views; a volume takes at most {_lib.TSDF_MAX_VIEWS} (its sums are 32-bit)")
+        self._call("dmvs_tsdf_integrate_f32", _ptr(depth), _ptr(valid), _ptr(rgb), v.ctypes.data_as(C.c_void_p), V, H, W, nx, ny, nz, origin,
+                   float(vol.h), float(tau), 0 if cull else _lib.TSDF_NO_CULL, _ptr(vol.S), _ptr(vol.Wt), _ptr(vol.C), self.stream())
+        vol.views += V
+        return vol
+
+    def tsdf_extract(self, vol, min_weight=1):
+        """dmvs_tsdf_flags_u8 / _vertices_f32 / _faces_i32 (include/dmvs.h): the surface-nets mesh of the volume's zero set over the voxels
+        with Wt >= min_weight.  -> (verts [N,3] fp32, rgb [N,3] uint8 (zeros without colour sums), faces [F,3] int32)"""
+        nx, ny, nz, origin = self._tsdf_vol("tsdf_extract", vol)
+        dev, n = self.device, nx * ny * nz
+        cell = torch.empty((nz, ny, nx), dtype=torch.uint8, device=dev)
+        quad = torch.empty((nz, ny, nx), dtype=torch.uint8, device=dev)
+        self._call("dmvs_tsdf_flags_u8", _ptr(vol.S), _ptr(vol.Wt), nx, ny, nz, int(min_weight), _ptr(cell), _ptr(quad), self.stream())
+        N = Q = 0
+        if n > 0:
+            cell_cum = torch.cumsum(cell.reshape(-1), 0, dtype=torch.int32)      # (N <= n < 2^31)
+            quad_cum = torch.cumsum(((quad & 1) + ((quad >> 1) & 1) + (quad >> 2)).reshape(-1), 0, dtype=torch.int64)
+            N, Q = int(cell_cum[-1]), int(quad_cum[-1])
+            if Q > _lib.TSDF_MAX_QUADS:
+                raise _lib.DmvsError(f"tsdf_extract: {Q} quads; at most {_lib.TSDF_MAX_QUADS} are supported (int32 face tables): use a coarser volume")
+            quad_cum = quad_cum.to(torch.int32)
+        verts = torch.empty((N, 3), dtype=torch.float32, device=dev)
+        rgb = torch.empty((N, 3), dtype=torch.uint8, device=dev)
+        faces = torch.empty((2 * Q, 3), dtype=torch.int32, device=dev)
+        if N > 0:
+            self._call("dmvs_tsdf_vertices_f32", _ptr(vol.S), _ptr(vol.Wt), _ptr(vol.C), nx, ny, nz, origin, float(vol.h), _ptr(cell), _ptr(cell_cum), N,
+                       _ptr(verts), _ptr(rgb), self.stream())
+        if Q > 0:
+            self._call("dmvs_tsdf_faces_i32", _ptr(vol.S), nx, ny, nz, _ptr(quad), _ptr(quad_cum), _ptr(cell_cum), Q, _ptr(faces), self.stream())
+        return verts, rgb, faces
+
+
+class TsdfVolume:
+    """The caller-owned state of dmvs_tsdf_integrate_f32 (include/dmvs.h), made zeroed by Ops.tsdf_volume: dims (nx, ny, nz), origin (HOST,
+    three doubles), h, S and Wt [nz,ny,nx] int32, C [nz,ny,nx,4] int32 holding the uint32 colour sums (torch has no arithmetic on uint32;
+    they stay below 2^24) or None, and `views`, how many views went in so far."""
+
+    def __init__(self, dims, origin, h, S, Wt, C):
+        self.dims, self.origin, self.h, self.S, self.Wt, self.C, self.views = tuple(dims), origin, h, S, Wt, C, 0

@@ -711,6 +711,73 @@ int dmvs_cloud_splat_sum_f32(const float* points, int64_t N, const double* trans
 int dmvs_depth_normals_f32(const float* depth, const uint8_t* valid, const double* cams, int64_t B, int32_t H, int32_t W,
                            int32_t radius, double rel_jump, int32_t min_pts, float* out, int64_t* counts, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * A surface from depth maps (added under ABI 4, additive; diffmvs_amd/mesh.py): a truncated signed distance volume averaged over all
+ * views, and its zero set as a surface-nets mesh.  Integer sums and fp64 geometry in a fixed order: every output is bitwise independent
+ * of the chunking and the order of the views, of the launch shape and of the run.
+ *
+ * The volume: dims (nx, ny, nz), nx ny nz < 2^31; origin: HOST, three doubles; h: the voxel side.  Voxel (i, j, k) samples the world
+ * point  X = ox + (double)i * h,  Y = oy + (double)j * h,  Z = oz + (double)k * h.  S, Wt: [nz,ny,nx] int32 (device, x fastest);
+ * C: NULL or [nz,ny,nx,4] uint32, the R, G, B sums and their count.  The caller zeroes them once; integration ADDS to them, so a scene
+ * can be streamed through in several calls.
+ *
+ * dmvs_tsdf_integrate_f32: depth [V,H,W] fp32 (device); valid: NULL or [V,H,W] uint8; rgb: NULL or [V,H,W,3] uint8 (needs C);
+ * views: HOST [V, DMVS_TSDF_VIEW_DOUBLES] doubles per view: rows 0 and 1 of P = K E[:3] (P00 .. P03, P10 .. P13), then row 2 of E
+ * (world -> camera); they go DMVS_TSDF_VIEW_CHUNK per launch as kernel arguments.  Per (voxel, view), pixel centres at integer
+ * coordinates, IEEE fp64 in exactly this order, no contraction:
+ *   x = ((P00 X + P01 Y) + P02 Z) + P03     y likewise with row 1     z = ((E20 X + E21 Y) + E22 Z) + E23
+ *   skip unless z > 0;   u = x / z,  v = y / z;   skip if u or v is not finite
+ *   pu = rint(u), pv = rint(v) (ties to even);   skip unless 0 <= pu <= W - 1 and 0 <= pv <= H - 1 (tested in fp64, then converted)
+ *   d = (double)depth[view][pv][pu];   skip unless (valid is NULL or valid[..] != 0) and d finite and d > 0
+ *   sdf = d - z;   skip if sdf < -tau
+ *   q = (int32)rint(fmin(sdf / tau, 1.0) * 16384.0);   S += q;   Wt += 1
+ *   if rgb and sdf <= tau:   C += (r, g, b, 1)
+ * One owner lane per voxel, plain read-modify-write, no atomics.  V <= DMVS_TSDF_MAX_VIEWS per call and over the life of a volume
+ * (the caller's to keep) bounds |S| below 2^30 and the colour sums below 2^24.  A workgroup skips a (brick of voxels, view) pair only
+ * when every voxel of the brick is provably behind the camera or off one side of the image (csrc/tsdf.hip has the argument): the
+ * volume is bitwise the same with flags = DMVS_TSDF_NO_CULL, which is there for A/B runs and the tests.
+ * V = 0, H W = 0 or an empty volume: nothing is touched.
+ * DMVS_EINVAL (before any launch): a negative dim, nx ny nz >= 2^31, NULL origin, origin or h not finite, h <= 0, V < 0 or
+ * V > DMVS_TSDF_MAX_VIEWS, H or W < 0, H W >= 2^31, tau not finite or <= 0, an unknown flag, rgb without C, NULL depth / views / S / Wt
+ * with work to do, a non-finite views entry, depth / S / Wt not 4-byte or C not 16-byte aligned.
+ *
+ * Extraction (surface nets: no case table).  A voxel is OBSERVED iff Wt >= min_weight (min_weight >= 1), its value is
+ * f = (double)S / (double)Wt, it is INSIDE iff S < 0.  Cell (i, j, k) of the (nx-1)(ny-1)(nz-1) cell grid has the corners c = 0 .. 7 at
+ * the offsets (c & 1, c >> 1 & 1, c >> 2 & 1) and gets a VERTEX iff all 8 are observed and at least one of its 12 edges has ends of
+ * different sign.  The edges are walked as the pairs (a, b), a < b, one bit apart, in lexicographic order: (0,1) (0,2) (0,4) (1,3)
+ * (1,5) (2,3) (2,6) (3,7) (4,5) (4,6) (5,7) (6,7); a crossing edge contributes the point offset(a) + t e_axis, t = f_a / (f_a - f_b);
+ * the three coordinates are summed in fp64 in that order and divided by the number of crossings; the vertex is
+ * origin + ((double)cell + mean) * h per axis, rounded once to fp32.  Its colour, with n the sum of the eight corners' counts, is
+ * (2 sum R + n) / (2 n) in integers, likewise G and B; 0 without C or with n = 0.  Vertices are numbered in ascending cell linear
+ * index (x fastest).  Faces: for voxel (i, j, k) in ascending linear index and axis a = x, y, z in that order, the edge to the +a
+ * neighbour, if that exists, both ends are observed and their signs differ, yields a quad over the cells at the offsets
+ * (b, c) = (-1,-1), (0,-1), (0,0), (-1,0) along the cyclically next axes b, c -- only if all four are in the cell grid and have a
+ * vertex; in that order if the voxel is inside, reversed otherwise (the normal points from inside to free space); the triangles are
+ * (q0, q1, q2), (q0, q2, q3).
+ *   dmvs_tsdf_flags_u8: cell [nz,ny,nx] uint8 = 1 where the cell whose lowest corner is the voxel has a vertex (0 on the upper
+ *     faces), quad [nz,ny,nx] uint8: bit a set where the voxel's +a edge yields a quad.  Two launches (quad reads cell).
+ *   The caller forms the INCLUSIVE running sums cell_cum, quad_cum [nz,ny,nx] int32 of cell and of popcount(quad), N = the number of
+ *     vertices and Q = the number of quads (their last entries).
+ *   dmvs_tsdf_vertices_f32: verts [N,3] fp32, rgb [N,3] uint8, vertex cell_cum - 1 of every flagged cell.
+ *   dmvs_tsdf_faces_i32: faces [2 Q,3] int32, quads quad_cum - popcount(quad) .. quad_cum - 1 of every voxel, in axis order.
+ * An empty volume, N = 0 or Q = 0: nothing is touched.  DMVS_EINVAL: the volume's cases above (origin and h where they are taken),
+ * min_weight < 1, N < 0 or N > nx ny nz, Q < 0, Q > 3 nx ny nz or Q > DMVS_TSDF_MAX_QUADS, a NULL array other than C with work to do,
+ * a misaligned int32 / fp32 array or C. */
+#define DMVS_TSDF_VIEW_CHUNK 8
+#define DMVS_TSDF_VIEW_DOUBLES 12
+#define DMVS_TSDF_MAX_VIEWS 65535
+#define DMVS_TSDF_MAX_QUADS 357913941 /* 6 Q int32 face entries below 2^31 */
+#define DMVS_TSDF_NO_CULL 0x1
+int dmvs_tsdf_integrate_f32(const float* depth, const uint8_t* valid, const uint8_t* rgb, const double* views, int64_t V, int32_t H, int32_t W,
+                            int32_t nx, int32_t ny, int32_t nz, const double* origin, double h, double tau, int32_t flags, int32_t* S,
+                            int32_t* Wt, uint32_t* C, void* stream);
+int dmvs_tsdf_flags_u8(const int32_t* S, const int32_t* Wt, int32_t nx, int32_t ny, int32_t nz, int32_t min_weight, uint8_t* cell,
+                       uint8_t* quad, void* stream);
+int dmvs_tsdf_vertices_f32(const int32_t* S, const int32_t* Wt, const uint32_t* C, int32_t nx, int32_t ny, int32_t nz, const double* origin,
+                           double h, const uint8_t* cell, const int32_t* cell_cum, int64_t N, float* verts, uint8_t* rgb, void* stream);
+int dmvs_tsdf_faces_i32(const int32_t* S, int32_t nx, int32_t ny, int32_t nz, const uint8_t* quad, const int32_t* quad_cum,
+                        const int32_t* cell_cum, int64_t Q, int32_t* faces, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
