@@ -589,7 +589,10 @@ class Ops:
         return gref, gsrc
 
     def getcost_bwd(self, ref, src, rt, inv_depth, confidence, view_w, disp_min, disp_max, n, interval, min_radius,
-                    max_radius, vw_shift, gcost, gsrc=None, G=4, gather=None):
+                    max_radius, vw_shift, gcost, gsrc=None, G=4, gather=None, worklist=None):
+        """-> gref [B,H,W,C], gsrc [S,B,H,W,C] (accumulated into `gsrc` if given).  `worklist`: caller-owned int32 scratch of
+        4 + 66 * ntiles entries (16x16 tiles; layout in csrc/warp_tile.h) used instead of the internal one, so that the caller can
+        read the tile dispatch back; ignored on the paths that take none (gather, C = 48, S > MAX_WINDOW_VIEWS)."""
         gather = self.tune.get("bwd_gather", False) if gather is None else gather
         self._chk(ref, src, rt, inv_depth, confidence, view_w, disp_min, disp_max, gcost, gsrc)
         B, H, W, Cc = ref.shape
@@ -598,7 +601,15 @@ class Ops:
         if gsrc is None:
             gsrc = torch.zeros_like(src)
         ntiles = B * ((H + 15) // 16) * ((W + 15) // 16)
-        wl = None if (gather or Cc == 48 or S > MAX_WINDOW_VIEWS) else torch.empty(4 + 66 * ntiles, dtype=torch.int32, device=self.device)
+        if gather or Cc == 48 or S > MAX_WINDOW_VIEWS:
+            wl = None
+        elif worklist is not None:
+            if worklist.dtype != torch.int32 or worklist.device != self.device or not worklist.is_contiguous() \
+                    or worklist.numel() < 4 + 66 * ntiles:
+                raise ValueError(f"worklist: contiguous int32 of at least {4 + 66 * ntiles} entries on {self.device}")
+            wl = worklist
+        else:
+            wl = torch.empty(4 + 66 * ntiles, dtype=torch.int32, device=self.device)
         d = _lib.GetCostDesc(ref=_ptr(ref), src=_ptr(src), rt=_ptr(rt), inv_depth=_ptr(inv_depth),
                              confidence=_ptr(confidence), view_w=_ptr(view_w), disp_min=_ptr(disp_min),
                              disp_max=_ptr(disp_max), out_cost=None, out_samples=None, worklist=_ptr(wl), B=B, S=S, C=Cc, G=G, n=n,

@@ -1199,8 +1199,9 @@ def test_warp_corr_init_backward(ops, C, monkeypatch):
 
 @pytest.mark.parametrize("H,W,D,scene", [(36, 44, 12, True), (20, 36, 7, False)])
 def test_warp_corr_init_backward_window_tiles(ops, H, W, D, scene):
-    """plane-sweep backward through LDS windows (C = 48): several tiles, depth chunks; synthetic cameras (windows fit) and
-    strongly rotated cameras (chunks scatter in global memory)"""
+    """plane-sweep backward through LDS windows (C = 48) against autograd through the fp32 oracle: several tiles incl. partial ones,
+    several depth chunks per tile; synthetic cameras and the mildly rotated _cams.  Every chunk of both cases fits the window (45 and 26
+    chunks); the global-memory chunks, skipped chunks and the pole plan are in test_warp_corr_init_backward_chunk_plans."""
     B, S, C = 2, 2, 48
     feats = [rnd(B, C, H, W, seed=90 + v).requires_grad_(True) for v in range(S + 1)]
     if scene:
@@ -1227,9 +1228,10 @@ def test_warp_corr_init_backward_window_tiles(ops, H, W, D, scene):
                                                         (32, 6, True, 36, 44, 2.0 / 384), (16, 4, True, 40, 24, 1.0 / 384),
                                                         (32, 4, False, 20, 36, 0.2)])
 def test_getcost_backward(ops, C, n, with_conf, H, W, interval, monkeypatch):
-    """grad_ref / grad_src of GetCost against autograd through the oracle: LDS-window kernel (several tiles, partial
-    tiles; the large interval sends the tiles to the per-pixel kernel through the worklist) and the per-pixel kernel, each with both
-    channel -> lane mappings of the scatter (DMVS_TUNE_BWD_INTERLEAVED)"""
+    """grad_ref / grad_src of GetCost against autograd through the fp32 oracle: LDS-window kernel (several tiles, partial tiles) and the
+    flat per-pixel kernel, each with both channel -> lane mappings of the scatter (DMVS_TUNE_BWD_INTERLEAVED).  With these cameras every
+    tile of every case fits the window, the interval of 0.2 included (worklist[0] == worklist[1] == 0 on 2, 18, 12 and 12 tiles): no tile is listed for
+    the per-pixel kernel.  Listed tiles and the stand-down are in test_getcost_backward_dispatch_paths."""
     B, S = 2, 3
     pm = _cams(B, S + 1, H, W, 5)
     feats = [rnd(B, C, H, W, seed=60 + v).requires_grad_(True) for v in range(S + 1)]
@@ -1264,6 +1266,593 @@ def test_view_aggregate_backward(ops):
     gcor, gw = ops.view_aggregate_bwd(*dev(ops, cor.detach(), w.detach(), out.detach(), gout))
     close(gcor, cor.grad, 1e-5)
     close(gw, w.grad, 1e-5)
+
+
+@pytest.mark.parametrize("B,S,G,D,H,W,zeros", [(2, 3, 4, 5, 19, 23, False), (3, 11, 1, 17, 20, 24, False), (2, 3, 4, 5, 19, 23, True)])
+def test_view_aggregate_backward_several_workgroups(ops, B, S, G, D, H, W, zeros):
+    """view_aggregate_bwd against the fp64 formula past one workgroup: 2622 and 15840 lanes of 256, so workgroups straddle view and
+    batch boundaries; `zeros`: two of the three views weigh exactly 0 at a tenth of the pixels (never all of them: 1 / 1e-8 would
+    set the scale and hide everything else)"""
+    cor, w = rnd(B, S, G, D, H, W, seed=1), rnd(B, S, H, W, seed=2, lo=0.05, hi=1)
+    if zeros:
+        hit = torch.from_numpy(np.random.RandomState(5).uniform(size=(B, H, W)) < 0.1)
+        keep = torch.from_numpy(np.random.RandomState(6).randint(0, S, size=(B, H, W)))
+        w[hit.unsqueeze(1) & (keep.unsqueeze(1) != torch.arange(S).view(1, S, 1, 1))] = 0.0
+        assert int(((w == 0).sum(1) == 2).sum()) == int(hit.sum()) > 0.05 * B * H * W and float(w.sum(1).min()) >= 0.05
+    gout = rnd(B, G, D, H, W, seed=3)
+    wsum32 = torch.full((B, H, W), 1e-8)
+    for s in range(S):
+        wsum32 = wsum32 + w[:, s]
+    out32 = ((cor * w.view(B, S, 1, 1, H, W)).sum(1) / wsum32.view(B, 1, 1, H, W))        # the forward's fp32 output: an input here
+    cor64, w64, go64, ws64 = cor.double(), w.double(), gout.double(), wsum32.double().view(B, 1, 1, 1, H, W)
+    want_gcor = go64.unsqueeze(1) * w64.view(B, S, 1, 1, H, W) / ws64
+    want_gw = (go64.unsqueeze(1) * (cor64 - out32.double().unsqueeze(1))).sum((2, 3)) / ws64.view(B, 1, H, W)
+    gcor, gw = ops.view_aggregate_bwd(*dev(ops, cor, w, out32, gout))
+    err64("view_aggregate_bwd gcor", gcor, want_gcor, 1e-5)
+    err64("view_aggregate_bwd gw", gw, want_gw, 1e-5)
+    if zeros:
+        assert torch.equal(gcor.cpu()[(w == 0).view(B, S, 1, 1, H, W).expand_as(cor)], torch.zeros(int((w == 0).sum()) * G * D))
+
+
+# ---- the warp backward kernels on every dispatch path, against fp64 built from the kernels' own fp32 inputs.
+# The fp32 oracle cannot judge them once the geometry is not mild: its own fp32 inverse and projection put 1e-4 .. 1e-3 of scale
+# between it and kernels that agree with each other to 1e-7.
+def _warp_coords(rt, depth, coords32=False):
+    """sampling positions of every hypothesis: rt [B,12] fp32, depth [B,D,H,W] fp32 -> u, v [B,D,H,W] fp64 and the finite mask.  Ray,
+    +1e-8 at z == 0, |u|, |v| < 1e9: the rules of project_uv (csrc/warp_tile.h).  coords32: evaluated by fp32 torch ops, then widened."""
+    B, _, H, W = depth.shape
+    dt = torch.float32 if coords32 else torch.float64
+    m = [rt[:, i].to(dt).view(B, 1, 1, 1) for i in range(12)]
+    d = depth.to(dt)
+    y, x = torch.meshgrid(torch.arange(H, dtype=dt), torch.arange(W, dtype=dt), indexing="ij")
+    rx, ry, rz = m[0] * x + m[1] * y + m[2], m[3] * x + m[4] * y + m[5], m[6] * x + m[7] * y + m[8]
+    px, py, pz = rx * d + m[9], ry * d + m[10], rz * d + m[11]
+    pz = torch.where(pz == 0, pz + 1e-8, pz)
+    u, v = (px / pz).double(), (py / pz).double()
+    return u, v, (u.abs() < 1e9) & (v.abs() < 1e9)           # NaN compares False
+
+
+def _warp64(src64, rt, depth, coords32=False):
+    """differentiable warping in fp64 from what the kernels are handed: src64 [B,C,Hs,Ws], rt [B,12] fp32 (ops.compose_proj), depth
+    [B,D,H,W] fp32 -> [B,C,D,H,W].  Positions from _warp_coords, then floor, per-tap bounds test, no behind-camera mask: the rules of
+    make_samp (csrc/warp_tile.h).  coords32: the sampling position (u, v) is evaluated by fp32 torch ops and then widened; everything
+    after it stays fp64 (the coordinate floor of _warp_ref)."""
+    B, C, Hs, Ws = src64.shape
+    D, H, W = depth.shape[1:]
+    u, v, fin = _warp_coords(rt, depth, coords32)
+    u, v = torch.where(fin, u, torch.full_like(u, -4.0)), torch.where(fin, v, torch.full_like(v, -4.0))
+    x0, y0 = u.floor(), v.floor()
+    wx1, wy1 = u - x0, v - y0
+    wx0, wy0 = 1 - wx1, 1 - wy1
+    flat = src64.reshape(B, C, Hs * Ws)
+    out = 0
+    for dx, dy, wgt in ((0, 0, wx0 * wy0), (1, 0, wx1 * wy0), (0, 1, wx0 * wy1), (1, 1, wx1 * wy1)):
+        xs, ys = x0 + dx, y0 + dy
+        ok = fin & (xs >= 0) & (xs <= Ws - 1) & (ys >= 0) & (ys <= Hs - 1)
+        idx = (ys.clamp(0, Hs - 1) * Ws + xs.clamp(0, Ws - 1)).long().reshape(B, 1, -1).expand(B, C, -1)
+        out = out + torch.gather(flat, 2, idx) * (wgt * ok).reshape(B, 1, -1)
+    return out.view(B, C, D, H, W)
+
+
+def _group_corr64(warped, ref64, G=4):
+    B, C, D, H, W = warped.shape
+    return (warped.view(B, G, C // G, D, H, W) * ref64.view(B, G, C // G, 1, H, W)).mean(2)
+
+
+def _sweep_depth32(disp_min, disp_max, D):
+    """the plane sweep's D depths per batch item as its kernels generate them, fp32: k / (D - 1) through dmvs_disp_to_depth -> [B,D]"""
+    nd = torch.arange(D, dtype=torch.float32) / torch.tensor(float(D - 1))
+    lo, hi = disp_min.view(-1, 1), disp_max.view(-1, 1)
+    return 1.0 / (lo + (hi - lo) * nd.view(1, -1)).clamp(min=1e-6)
+
+
+def _getcost_depth32(inv, conf, n, interval, rmin, rmax, disp_min, disp_max):
+    """GetCost's n depths per pixel, fp32, in the op order of tile_pixel / hyp_depth (csrc/warp_tile.h) -> [B,n,H,W]"""
+    f = lambda v: torch.tensor(v, dtype=torch.float32)
+    cur = inv.squeeze(1)
+    radius = f(float(n // 2)) * f(interval)
+    if conf is not None:
+        r0, r1 = f(rmin) * radius, f(rmax) * radius
+        radius = r0 + (1.0 - conf) * (r1 - r0)
+    lo = cur - radius
+    step = (cur + radius - lo) / f(float(n - 1))
+    sk = torch.arange(n, dtype=torch.float32).view(1, n, 1, 1) * step.unsqueeze(1)
+    sk = (sk + lo.unsqueeze(1)).clamp(0.0, 1.0)
+    dlo, dhi = disp_min.view(-1, 1, 1, 1), disp_max.view(-1, 1, 1, 1)
+    return 1.0 / (dlo + (dhi - dlo) * sk).clamp(min=1e-6)
+
+
+def _sweep_grads64(feats, rt, depth, gcor, coords32):
+    """fp64 gradients of sum(gcor * cor), cor[b,s] = group_corr(warp(src_s), ref), w.r.t. the V feature maps (NCHW) -> V tensors"""
+    f64 = [f.double().requires_grad_(True) for f in feats]
+    cor = torch.stack([_group_corr64(_warp64(f64[s + 1], rt[:, s], depth, coords32), f64[0]) for s in range(len(feats) - 1)], 1)
+    (cor * gcor.double()).sum().backward()
+    return [f.grad for f in f64]
+
+
+def _getcost_grads64(feats, rt, depth, vw_up, gcost, coords32):
+    """the same through GetCost's weighted view mean; vw_up [B,S,H,W]: the view weights after the nearest upsample.  wsum is the kernels'
+    fp32 sum 1e-8 + w_0 + w_1 + ... in view order, widened."""
+    f64 = [f.double().requires_grad_(True) for f in feats]
+    B, S, H, W = vw_up.shape
+    wsum = torch.full((B, H, W), 1e-8)
+    acc = 0
+    for s in range(S):
+        wsum = wsum + vw_up[:, s]
+        acc = acc + vw_up[:, s].double().view(B, 1, 1, H, W) * _group_corr64(_warp64(f64[s + 1], rt[:, s], depth, coords32), f64[0])
+    cost = acc / wsum.double().view(B, 1, 1, H, W)
+    (cost.reshape(gcost.shape) * gcost.double()).sum().backward()
+    return [f.grad for f in f64]
+
+
+_WarpRef = collections.namedtuple("_WarpRef", "grads floor")        # fp64 gradients per feature map (NCHW), the coordinate floor
+
+
+def _warp_ref(fn, *args):
+    """the reference gradients and the coordinate floor: the largest difference between them and the same fp64 evaluation at sampling
+    positions rounded the way any fp32 evaluation rounds them.  It says how far fp32 coordinates alone can move the gradient, and it
+    never looks at the code under test."""
+    g64, g32 = fn(*args, False), fn(*args, True)
+    return _WarpRef(g64, max(float((a - b).abs().max()) for a, b in zip(g64, g32)))
+
+
+def _warp_check(what, got_nhwc, want, floor, pole=False):
+    """max abs err <= 4 * floor + 2^-20 * scale, scale = max(1, max |want|).  4: the kernel's own, equally valid fp32 evaluation of the
+    coordinates (fma contraction, reciprocal + Newton step, atomic order); 2^-20: fp32 accumulation over at most S * n * 4 (S * D * 4)
+    terms.  Without a projection pole in the depth range the bound has to undercut the 1e-4 the fp32 oracle is given."""
+    got = got_nhwc.detach().cpu()
+    assert got.dtype == torch.float32 and torch.isfinite(got).all(), what
+    got = got.permute(0, 3, 1, 2).double()
+    assert got.shape == want.shape, (got.shape, want.shape)
+    scale = max(1.0, float(want.abs().max()))
+    err, bound = float((got - want).abs().max()), 4 * floor + 2.0 ** -20 * scale
+    print(f"{what}: max abs err vs fp64 {err:.3e}, coordinate floor {floor:.3e}, bound {bound:.3e} (scale {scale:.3e})")
+    assert pole or bound < 1e-4 * scale, f"{what}: badly conditioned input, bound {bound:.3e} at scale {scale:.3e}"
+    assert err <= bound, f"{what}: max abs err {err:.3e} > {bound:.3e} (floor {floor:.3e}, scale {scale:.3e})"
+    return err
+
+
+def _rot(yaw=0.0, roll=0.0):
+    """roll about the optical axis after yaw about the vertical one"""
+    cy, sy, cr, sr = np.cos(yaw), np.sin(yaw), np.cos(roll), np.sin(roll)
+    return np.array([[cr, -sr, 0], [sr, cr, 0], [0, 0, 1]]) @ np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]])
+
+
+def _cams_bwd(name, B, V, H, W, Hs=None, Ws=None):
+    """the camera sets of the backward cases [B,V,2,4,4]: _cams, then per name other poses / intrinsics of the source views"""
+    pm = _cams(B, V, H, W, 5).numpy().copy()
+    for b in range(B):
+        for v in range(1, V):
+            E, Kc = pm[b, v, 0], pm[b, v, 1]
+            if name in ("base100", "rolled", "rolled15"):         # translations x 4: GetCost footprints outgrow the window
+                E[:3, 3] *= 4.0
+            if name in ("rolled", "rolled15"):                    # source views rolled 45 degrees, longer focal length
+                E[:3, :3] = _rot(0.06 * v + 0.01 * b, np.pi / 4)
+                Kc[0, 0] = Kc[1, 1] = 1.1 * W * (1.3 if name == "rolled" else 1.5)
+            if name == "rot05":                                   # 0.5 rad per view: most samples out of bounds, some behind the camera
+                E[:3, :3] = _rot(0.5 * v)
+                E[:3, 3] = [-150.0 * v, 20.0 * v, 5.0 * b]
+            if name in ("pole", "pole_z0") and v == 1:            # looks along the baseline: the plane z = 0 crosses the depth range
+                E[:3, :3] = _rot(np.pi / 2)
+                E[:3, 3] = [-650.0, 0.0, 100.0]
+            if name in ("z0", "pole_z0") and v == 2:              # z = 0 everywhere -> the +1e-8 rule -> non-finite coordinates
+                E[2, :] = 0.0
+            if name == "behind" and v == 2:                       # turned away: every point is behind this camera
+                E[:3, :3] = _rot(np.pi)
+            if name == "identity" and v == 1:
+                pm[b, v] = pm[b, 0]
+            if name == "inside" and v == 1 and b == 0:
+                # stands in the scene, 600 ahead on the ray of pixel (16, 16), and looks the same way through a short lens: z = 0 lies
+                # inside the depth range, yet the two end hypotheses of the tiles around that pixel project into a small box
+                E[:3, :3] = np.eye(3)
+                E[:3, 3] = -600.0 * (np.linalg.inv(pm[b, 0, 1, :3, :3]) @ [16.0, 16.0, 1.0])
+                Kc[0, 0] = Kc[1, 1] = 1.1 * W / 16
+            if name == "padding" and v == 2:                      # principal point far off: every tap of every sample is padding
+                Kc[0, 2] += 40.0 * W
+            if Hs is not None:                                    # source images on a grid of their own
+                Kc[0, 0] = Kc[1, 1] = Kc[0, 0] * Ws / W
+                Kc[0, 2], Kc[1, 2] = Kc[0, 2] * Ws / W, Hs / 2
+    return torch.from_numpy(pm)
+
+
+def _smooth_maps(B, H, W):
+    """inverse depth 0.3 + 0.4 x / W and confidence 1 - x / W: a surface, not noise"""
+    x = torch.arange(W, dtype=torch.float32).view(1, 1, W).expand(B, H, W) / W
+    return (0.3 + 0.4 * x).unsqueeze(1).contiguous(), (1.0 - x).contiguous()
+
+
+def _init_chunk_plan(rt, depth, D, H, W, Hs, Ws):
+    """fp64 replica of the plan of warp_init_bwd_win_kernel (csrc/warp_init_bwd_win.hip): rt [B,S,12], depth [B,D] (the kernel's fp32
+    table).  Per (16x16 tile, view) the whole-range footprint box and nchunk, per chunk its class: "fit" (box <= 24 x 20: LDS window),
+    "global" (taps and atomics straight in global memory), "skipped" (every tap is padding).  "pole" counts the workgroups whose
+    whole-range segment test fails (a projection pole inside the depth range: D / 4 chunks).  A coverage statement, not a numerical
+    one: a borderline fp32 / fp64 disagreement moves a chunk between classes, which is why the callers ask for at least 3 of each."""
+    B, S = rt.shape[:2]
+    m = rt.double().view(B, S, 12, 1, 1, 1)
+    d = depth.double().view(B, 1, D, 1, 1)
+    y, x = torch.meshgrid(torch.arange(H, dtype=torch.float64), torch.arange(W, dtype=torch.float64), indexing="ij")
+    rx, ry, rz = (m[:, :, 3 * i] * x + m[:, :, 3 * i + 1] * y + m[:, :, 3 * i + 2] for i in range(3))
+    px, py, pz = rx * d + m[:, :, 9], ry * d + m[:, :, 10], rz * d + m[:, :, 11]           # [B,S,D,H,W]
+    pz = torch.where(pz == 0, pz + 1e-8, pz)
+    u, v = px / pz, py / pz
+    fin = (u.abs() < 1e9) & (v.abs() < 1e9)
+
+    def plane_box(b, s, ys, xs, ka, kb):
+        sel = lambda t, k: t[b, s, k, ys, xs]
+        bad = ~sel(fin, ka) | ~sel(fin, kb) | ((sel(pz, ka) < 0) != (sel(pz, kb) < 0))
+        if bool(bad.any()):
+            return False, 0, 0
+        lx = torch.minimum(sel(u, ka), sel(u, kb)).floor().clamp(min=0)
+        hx = (torch.maximum(sel(u, ka), sel(u, kb)).floor() + 1).clamp(max=Ws - 1)
+        ly = torch.minimum(sel(v, ka), sel(v, kb)).floor().clamp(min=0)
+        hy = (torch.maximum(sel(v, ka), sel(v, kb)).floor() + 1).clamp(max=Hs - 1)
+        inc = (lx <= hx) & (ly <= hy)
+        if not bool(inc.any()):
+            return True, 0, 0
+        return True, int(hx[inc].max() - lx[inc].min()) + 1, int(hy[inc].max() - ly[inc].min()) + 1
+
+    plan = collections.Counter(fit=0, skipped=0, pole=0)
+    plan["global"] = 0
+    for b in range(B):
+        for ty in range(0, H, 16):
+            for tx in range(0, W, 16):
+                ys, xs = slice(ty, min(ty + 16, H)), slice(tx, min(tx + 16, W))
+                for s in range(S):
+                    seg, fnc, fnr = plane_box(b, s, ys, xs, 0, D - 1)
+                    nchunk = 1
+                    if seg and fnc > 0:
+                        nchunk = 1 + max((max(fnc - 19, 0) + 4) // 5, max(fnr - 19, 0))
+                    elif not seg:
+                        nchunk = max(D // 4, 1)
+                        plan["pole"] += 1
+                    dc = -(-D // min(nchunk, D))
+                    for k0 in range(0, D, dc):
+                        okseg, nc, nr = plane_box(b, s, ys, xs, k0, min(k0 + dc, D) - 1)
+                        plan["skipped" if okseg and nc <= 0 else "fit" if okseg and nc <= 24 and nr <= 20 else "global"] += 1
+    return plan
+
+
+def _getcost_tile_plan(rt, depth, H, W, win_h):
+    """fp64 replica of tile_boxes (csrc/warp_tile.h) for the two end hypotheses depth[:, 0], depth[:, -1] ([B,n,H,W], the kernels' fp32
+    depths): per 16x16 tile, in tile order, "fit", "box" (some view's footprint box exceeds the 24 x win_h window) or "pole" (the boxes
+    of the end points fit in every view and only the pole test, z changing sign between a pixel's ends, flags the tile).  A coverage
+    statement like _init_chunk_plan."""
+    B, S = rt.shape[:2]
+    m = rt.double().view(B, S, 12, 1, 1)
+    y, x = torch.meshgrid(torch.arange(H, dtype=torch.float64), torch.arange(W, dtype=torch.float64), indexing="ij")
+    rx, ry, rz = (m[:, :, 3 * i] * x + m[:, :, 3 * i + 1] * y + m[:, :, 3 * i + 2] for i in range(3))
+    ends = []
+    for d in (depth[:, 0], depth[:, -1]):
+        d = d.double().unsqueeze(1)
+        pz = rz * d + m[:, :, 11]
+        pz = torch.where(pz == 0, pz + 1e-8, pz)
+        ends.append(((rx * d + m[:, :, 9]) / pz, (ry * d + m[:, :, 10]) / pz, pz))
+    (u0, v0, z0), (u1, v1, z1) = ends
+    fin = (u0.abs() < 1e9) & (v0.abs() < 1e9) & (u1.abs() < 1e9) & (v1.abs() < 1e9)
+    pole = (z0 < 0) != (z1 < 0)
+    lx, hx = torch.minimum(u0, u1).floor().clamp(min=0), (torch.maximum(u0, u1).floor() + 1).clamp(max=W - 1)
+    ly, hy = torch.minimum(v0, v1).floor().clamp(min=0), (torch.maximum(v0, v1).floor() + 1).clamp(max=H - 1)
+    inc = fin & (lx <= hx) & (ly <= hy)
+    plan = []
+    for b in range(B):
+        for ty in range(0, H, 16):
+            for tx in range(0, W, 16):
+                t = (b, slice(None), slice(ty, ty + 16), slice(tx, tx + 16))
+                big = bool((~fin[t]).any())
+                for s in range(S):
+                    k = inc[t][s]
+                    if bool(k.any()):
+                        big |= int(hx[t][s][k].max() - lx[t][s][k].min()) + 1 > 24 or int(hy[t][s][k].max() - ly[t][s][k].min()) + 1 > win_h
+                plan.append("box" if big else "pole" if bool(pole[t].any()) else "fit")
+    return plan
+
+
+_GCB = collections.namedtuple("_GCB", "C n shift il cams maps interval H W path")
+_GETCOST_BWD = {
+    "all_window": _GCB(32, 6, 1, False, "cams", "noise", 2.0 / 384, 36, 44, "window"),
+    "mix_smooth": _GCB(32, 6, 1, False, "base100", "smooth", 0.05, 36, 44, "mix"),
+    "mix_noise_shift2_interleaved": _GCB(32, 6, 2, True, "base100", "noise", 0.05, 36, 44, "mix"),
+    "mix_noise_c16_shift0": _GCB(16, 4, 0, False, "base100", "noise", 0.05, 36, 44, "mix"),
+    "pole_tiles": _GCB(32, 6, 1, False, "inside", "smooth", 0.05, 36, 44, "pole_mix"),
+    "stand_down": _GCB(32, 4, 1, True, "pole", "noise", 0.1, 36, 44, "stand_down"),
+    "stand_down_z0": _GCB(16, 6, 1, False, "pole_z0", "noise", 0.1, 20, 36, "stand_down_all"),
+    "big_rotation": _GCB(32, 6, 1, False, "rot05", "noise", 0.05, 36, 44, "any"),
+    "rolled_source": _GCB(16, 4, 2, True, "rolled", "noise", 0.05, 36, 44, "mix"),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def _getcost_bwd_case(name):
+    """inputs (fp32, CPU) and the fp64 reference of a GetCost backward case: computed once, shared, never written to"""
+    c = _GETCOST_BWD[name]
+    B, S, H, W = 2, 3, c.H, c.W
+    pm = _cams_bwd(c.cams, B, S + 1, H, W)
+    feats = [rnd(B, c.C, H, W, seed=60 + v) for v in range(S + 1)]
+    if c.maps == "smooth":
+        inv, conf = _smooth_maps(B, H, W)
+    else:
+        inv, conf = rnd(B, 1, H, W, seed=70, lo=-0.1, hi=1.1), rnd(B, H, W, seed=71, lo=0.0, hi=1.0)
+    vw = rnd(B, S, H >> c.shift, W >> c.shift, seed=72, lo=0.0, hi=1.0)
+    disp_min, disp_max = _disp_range(B)
+    gcost = rnd(B, 4 * c.n, H, W, seed=73)
+    return dict(c=c, pm=pm, feats=feats, inv=inv, conf=conf, vw=vw, disp_min=disp_min, disp_max=disp_max, gcost=gcost, ref={})
+
+
+def _getcost_bwd_ref(case, rt):
+    """the reference depends on rt, the kernels' own input, which the backend computes: one reference per distinct rt (the emulation
+    and the device may round compose_proj differently)"""
+    key = rt.numpy().tobytes()
+    if key not in case["ref"]:
+        c = case["c"]
+        depth = _getcost_depth32(case["inv"], case["conf"], c.n, c.interval, 0.25, 4.0, case["disp_min"], case["disp_max"])
+        vw_up = case["vw"].repeat_interleave(1 << c.shift, 2).repeat_interleave(1 << c.shift, 3)
+        case["ref"][key] = _warp_ref(_getcost_grads64, case["feats"], rt, depth, vw_up, case["gcost"])
+    return case["ref"][key]
+
+
+def _getcost_bwd_run(ops, case, gather, worklist=None, gsrc=None):
+    c = case["c"]
+    feats = case["feats"]
+    rt = ops.compose_proj(dev(ops, case["pm"]))
+    gref, gsrc = ops.getcost_bwd(dev(ops, feats[0].permute(0, 2, 3, 1)), dev(ops, torch.stack([f.permute(0, 2, 3, 1) for f in feats[1:]])),
+                                 rt, dev(ops, case["inv"]), dev(ops, case["conf"]), dev(ops, case["vw"]), dev(ops, case["disp_min"]),
+                                 dev(ops, case["disp_max"]), c.n, c.interval, 0.25, 4.0, c.shift, dev(ops, case["gcost"]), gsrc=gsrc,
+                                 gather=gather, worklist=worklist)
+    return rt.cpu(), gref, gsrc
+
+
+def _getcost_bwd_compare(what, ref, gref, gsrc, pole=False):
+    errs = [_warp_check(f"{what} gref", gref, ref.grads[0], ref.floor, pole)]
+    errs += [_warp_check(f"{what} gsrc[{v}]", gsrc[v], ref.grads[v + 1], ref.floor, pole) for v in range(gsrc.shape[0])]
+    return max(errs)
+
+
+@pytest.mark.parametrize("name", list(_GETCOST_BWD))
+def test_getcost_backward_dispatch_paths(ops, name, monkeypatch):
+    """GetCost backward as training runs it (hybrid, worklist on) with the path it took read back from the worklist and asserted: every
+    tile through the LDS window, window and listed tiles mixed (the TILED per-pixel kernel), tiles that only the pole test of tile_boxes
+    lists, the stand-down (the per-pixel kernel takes every tile); then the flat per-pixel kernel on the same inputs.  Both against
+    fp64 on grad_ref (every element: unwritten ones would be NaN) and every view's grad_src."""
+    case = _getcost_bwd_case(name)
+    c = case["c"]
+    B = case["feats"][0].shape[0]
+    monkeypatch.setattr(ops, "debug_fill", float("nan"))
+    monkeypatch.setitem(ops.tune, "bwd_il", c.il)
+    ntiles = B * ((c.H + 15) // 16) * ((c.W + 15) // 16)
+    wl = torch.full((4 + 66 * ntiles,), -1, dtype=torch.int32, device=ops.device)
+    rt, gref, gsrc = _getcost_bwd_run(ops, case, False, worklist=wl)
+    wl = wl.cpu()
+    listed, mode, flags = int(wl[0]), int(wl[1]), wl[4:4 + ntiles]
+    print(f"getcost_bwd {name}: {listed} of {ntiles} tiles listed, mode {mode}")
+    assert listed == int(flags.sum()) and set(flags.tolist()) <= {0, 1} and mode in (0, 1)
+    assert wl[4 + ntiles:4 + ntiles + listed].tolist() == torch.nonzero(flags).flatten().tolist()
+    if c.path == "window":
+        assert listed == 0 and mode == 0
+    elif c.path == "mix":
+        assert 0 < listed < ntiles and mode == 0
+    elif c.path == "pole_mix":          # tiles that only the pole test of tile_boxes keeps away from the window kernel
+        depth = _getcost_depth32(case["inv"], case["conf"], c.n, c.interval, 0.25, 4.0, case["disp_min"], case["disp_max"])
+        plan = _getcost_tile_plan(rt, depth, c.H, c.W, 22 if c.C == 32 else 24)
+        print(f"getcost_bwd {name}: tile plan {plan}, flags {flags.tolist()}")
+        assert 0 < listed < ntiles and mode == 0 and sum(p == "pole" and f == 1 for p, f in zip(plan, flags.tolist())) >= 3
+    elif c.path == "stand_down":
+        assert mode == 1
+    elif c.path == "stand_down_all":
+        assert mode == 1 and listed == ntiles
+    ref = _getcost_bwd_ref(case, rt)
+    pole = c.cams in ("pole", "pole_z0", "inside")
+    _getcost_bwd_compare(f"getcost_bwd {name} hybrid", ref, gref, gsrc, pole)
+    if c.cams == "pole_z0":         # non-finite coordinates: no tap, no gradient, on either kernel
+        assert float(ref.grads[2].abs().max()) == 0.0 and torch.equal(gsrc[1].cpu(), torch.zeros_like(gsrc[1].cpu()))
+    rt_g, gref_g, gsrc_g = _getcost_bwd_run(ops, case, True)
+    assert torch.equal(rt, rt_g)
+    _getcost_bwd_compare(f"getcost_bwd {name} per-pixel", ref, gref_g, gsrc_g, pole)
+    if c.cams == "pole_z0":
+        assert torch.equal(gsrc_g[1].cpu(), torch.zeros_like(gsrc_g[1].cpu()))
+
+
+def test_getcost_backward_c48_new_geometry(ops, monkeypatch):
+    """C = 48 has no window kernel: the flat per-pixel kernel, both lane mappings, on the rolled-source geometry"""
+    case = dict(_getcost_bwd_case("rolled_source"))
+    B, _, H, W = case["feats"][0].shape
+    case["feats"] = [rnd(B, 48, H, W, seed=160 + v) for v in range(4)]
+    case["ref"] = {}
+    monkeypatch.setattr(ops, "debug_fill", float("nan"))
+    for il in (False, True):
+        monkeypatch.setitem(ops.tune, "bwd_il", il)
+        rt, gref, gsrc = _getcost_bwd_run(ops, case, False)          # C = 48: the worklist path is not taken
+        _getcost_bwd_compare(f"getcost_bwd C=48 interleaved={il}", _getcost_bwd_ref(case, rt), gref, gsrc)
+
+
+def test_getcost_backward_accumulates_into_grad_src(ops, monkeypatch):
+    """the contract of gsrc= is +=: pre-filled with P, the hybrid launch (window flush, listed tiles) returns P + grad"""
+    case = _getcost_bwd_case("mix_smooth")
+    monkeypatch.setitem(ops.tune, "bwd_il", case["c"].il)
+    S, (B, C, H, W) = 3, case["feats"][0].shape
+    P = rnd(S, B, H, W, C, seed=74)
+    wl = torch.zeros(4 + 66 * 18, dtype=torch.int32, device=ops.device)
+    rt, gref, gsrc = _getcost_bwd_run(ops, case, False, worklist=wl, gsrc=dev(ops, P.clone()))
+    assert 0 < int(wl[0]) < 18 and int(wl[1]) == 0
+    ref = _getcost_bwd_ref(case, rt)
+    for v in range(S):
+        _warp_check(f"getcost_bwd P + grad_src[{v}]", gsrc[v], ref.grads[v + 1] + P[v].permute(0, 3, 1, 2).double(), ref.floor)
+
+
+_WIB = collections.namedtuple("_WIB", "cams D H W Hs Ws S plan")
+_SWEEP_BWD = {
+    "global_and_skipped": _WIB("rot05", 12, 36, 44, 36, 44, 2, dict(fit=3, skipped=3, **{"global": 3})),
+    "mostly_global": _WIB("rolled15", 12, 36, 44, 36, 44, 2, "global>fit"),
+    "source_grid": _WIB("rolled15", 9, 36, 44, 27, 52, 2, "global>fit"),
+    "pole": _WIB("pole", 12, 36, 44, 36, 44, 2, dict(pole=3)),
+    "pole_inside": _WIB("inside", 12, 36, 44, 36, 44, 2, dict(pole=3, fit=3, **{"global": 3})),
+    "behind": _WIB("behind", 7, 36, 44, 36, 44, 2, None),
+    "identity": _WIB("identity", 7, 36, 44, 36, 44, 2, None),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def _sweep_bwd_case(name, C=48):
+    c = _SWEEP_BWD[name]
+    B = 2
+    different = (c.Hs, c.Ws) != (c.H, c.W)
+    pm = _cams_bwd(c.cams, B, c.S + 1, c.H, c.W, *((c.Hs, c.Ws) if different else ()))
+    feats = [rnd(B, C, c.H, c.W, seed=90)] + [rnd(B, C, c.Hs, c.Ws, seed=90 + v) for v in range(1, c.S + 1)]
+    disp_min, disp_max = _disp_range(B)
+    gcor = rnd(B, c.S, 4, c.D, c.H, c.W, seed=95)
+    return dict(c=c, pm=pm, feats=feats, disp_min=disp_min, disp_max=disp_max, gcor=gcor, ref={})
+
+
+def _sweep_bwd_ref(case, rt):
+    key = rt.numpy().tobytes()
+    if key not in case["ref"]:
+        c = case["c"]
+        depth = _sweep_depth32(case["disp_min"], case["disp_max"], c.D).view(-1, c.D, 1, 1).expand(-1, c.D, c.H, c.W)
+        case["ref"][key] = _warp_ref(_sweep_grads64, case["feats"], rt, depth, case["gcor"])
+    return case["ref"][key]
+
+
+def _sweep_bwd_run(ops, case, gather, gsrc=None):
+    feats = case["feats"]
+    rt = ops.compose_proj(dev(ops, case["pm"]))
+    gref, gsrc = ops.warp_corr_init_bwd(dev(ops, feats[0].permute(0, 2, 3, 1)), dev(ops, torch.stack([f.permute(0, 2, 3, 1) for f in feats[1:]])),
+                                        rt, dev(ops, case["disp_min"]), dev(ops, case["disp_max"]), dev(ops, case["gcor"]), gsrc=gsrc,
+                                        gather=gather)
+    return rt.cpu(), gref, gsrc
+
+
+@pytest.mark.parametrize("name", list(_SWEEP_BWD))
+def test_warp_corr_init_backward_chunk_plans(ops, name, monkeypatch):
+    """plane-sweep backward (C = 48) through the LDS-window kernel with its chunk plan asserted from an fp64 replica: chunks that fit
+    the window, chunks that read and scatter in global memory, chunks skipped as padding, the D / 4 plan around a projection pole; a
+    source grid of its own, a view behind the camera, the identity homography.  Then the per-pixel kernel in both lane mappings.
+    All against fp64 on grad_ref (every element) and every view's grad_src."""
+    case = _sweep_bwd_case(name)
+    c = case["c"]
+    monkeypatch.setattr(ops, "debug_fill", float("nan"))
+    rt, gref, gsrc = _sweep_bwd_run(ops, case, False)
+    plan = _init_chunk_plan(rt, _sweep_depth32(case["disp_min"], case["disp_max"], c.D), c.D, c.H, c.W, c.Hs, c.Ws)
+    print(f"warp_corr_init_bwd {name}: chunk plan {dict(plan)}")
+    if isinstance(c.plan, dict):
+        assert all(plan[k] >= n for k, n in c.plan.items()), plan
+    elif c.plan == "global>fit":
+        assert plan["global"] > plan["fit"] >= 3, plan
+    ref = _sweep_bwd_ref(case, rt)
+    pole = c.cams in ("pole", "inside")
+    if pole:
+        # the pole view must see the scene, or the case proves nothing.  "pole": both batch items carry the pole view, each is held to
+        # the 10 %; "inside": only item 0 does (item 1 keeps a mild camera, which would pass on its own and say nothing)
+        for b in range(1 if c.cams == "inside" else 2):
+            seen = float((ref.grads[1][b] != 0).double().mean())
+            print(f"warp_corr_init_bwd {name}: the pole view's grad_src is non-zero on {100 * seen:.0f} % of its texels, item {b}")
+            assert seen >= 0.1
+    if c.cams == "behind":
+        assert float((ref.grads[2] != 0).double().mean()) >= 0.1
+    if c.cams == "identity":
+        # what the case is for: sampling positions that are exact integers (the floor / weight-0 edge) and x0 + 1 == Ws on the last
+        # column.  rt comes from the backend's compose_proj, so that it is the identity is asserted, not assumed: 2^-24 is half an ulp
+        # of 1, and a translation below it vanishes against x * depth (depth >= 300).  Then the edge itself, from the reference's own
+        # fp64 positions: at least half of the samples with an exactly integer u, at least half of the last column's B * D * H
+        # samples with floor(u) + 1 == Ws.
+        off = float((rt[:, 0] - torch.tensor([1., 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0])).abs().max())
+        depth = _sweep_depth32(case["disp_min"], case["disp_max"], c.D).view(-1, c.D, 1, 1).expand(-1, c.D, c.H, c.W)
+        u, v, fin = _warp_coords(rt[:, 0], depth)
+        exact = int((fin & (u == u.floor())).sum())
+        last = int((fin & (u.floor() + 1 == c.Ws)).sum())
+        print(f"warp_corr_init_bwd identity: max |rt - identity| {off:.3e}, {exact} of {u.numel()} samples with an integer u, "
+              f"{last} with x0 + 1 == Ws")
+        assert off <= 2.0 ** -24
+        assert 2 * exact >= u.numel() and 2 * last >= 2 * c.D * c.H
+    errs = {"window": [_warp_check(f"warp_corr_init_bwd {name} window gref", gref, ref.grads[0], ref.floor, pole)]
+            + [_warp_check(f"warp_corr_init_bwd {name} window gsrc[{v}]", gsrc[v], ref.grads[v + 1], ref.floor, pole) for v in range(c.S)]}
+    for il in (False, True):
+        monkeypatch.setitem(ops.tune, "bwd_il", il)
+        rt_g, gref, gsrc = _sweep_bwd_run(ops, case, True)
+        assert torch.equal(rt, rt_g)
+        _warp_check(f"warp_corr_init_bwd {name} per-pixel interleaved={il} gref", gref, ref.grads[0], ref.floor, pole)
+        for v in range(c.S):
+            _warp_check(f"warp_corr_init_bwd {name} per-pixel interleaved={il} gsrc[{v}]", gsrc[v], ref.grads[v + 1], ref.floor, pole)
+
+
+@pytest.mark.parametrize("C", [32, 16])
+@pytest.mark.parametrize("name", list(_SWEEP_BWD))
+def test_warp_corr_init_backward_per_pixel_c32_c16(ops, name, C, monkeypatch):
+    """the per-pixel plane-sweep kernel at C = 32 and 16, both lane mappings, on every geometry of the chunk-plan cases"""
+    case = _sweep_bwd_case(name, C)
+    pole = case["c"].cams in ("pole", "inside")
+    monkeypatch.setattr(ops, "debug_fill", float("nan"))
+    for il in (False, True):
+        monkeypatch.setitem(ops.tune, "bwd_il", il)
+        rt, gref, gsrc = _sweep_bwd_run(ops, case, True)
+        ref = _sweep_bwd_ref(case, rt)
+        _warp_check(f"warp_corr_init_bwd {name} C={C} interleaved={il} gref", gref, ref.grads[0], ref.floor, pole)
+        for v in range(case["c"].S):
+            _warp_check(f"warp_corr_init_bwd {name} C={C} interleaved={il} gsrc[{v}]", gsrc[v], ref.grads[v + 1], ref.floor, pole)
+
+
+@pytest.mark.parametrize("gather", [False, True])
+def test_warp_corr_init_backward_accumulates_into_grad_src(ops, gather, monkeypatch):
+    """the contract of gsrc= is +=, on the window kernel (window flushes and global chunks) and on the per-pixel kernel"""
+    case = _sweep_bwd_case("global_and_skipped")
+    c = case["c"]
+    monkeypatch.setitem(ops.tune, "bwd_il", False)
+    P = rnd(c.S, 2, c.Hs, c.Ws, 48, seed=96)
+    rt, gref, gsrc = _sweep_bwd_run(ops, case, gather, gsrc=dev(ops, P.clone()))
+    ref = _sweep_bwd_ref(case, rt)
+    for v in range(c.S):
+        _warp_check(f"warp_corr_init_bwd gather={gather} P + grad_src[{v}]", gsrc[v], ref.grads[v + 1] + P[v].permute(0, 3, 1, 2).double(),
+                    ref.floor)
+
+
+def test_warp_backward_padding_view_gets_exact_zero(ops, monkeypatch):
+    """a view whose every tap is padding gets grad_src == 0 exactly, from every kernel: the window kernels skip it (empty box), the
+    per-pixel kernels flush nothing"""
+    B, S, H, W = 2, 2, 20, 36
+    pm = _cams_bwd("padding", B, S + 1, H, W)
+    disp_min, disp_max = dev(ops, *_disp_range(B))
+    rt = ops.compose_proj(dev(ops, pm))
+    monkeypatch.setattr(ops, "debug_fill", float("nan"))
+    for C in (48, 32):
+        feats = [rnd(B, H, W, C, seed=120 + v) for v in range(S + 1)]
+        ref_f, src_f = dev(ops, feats[0]), dev(ops, torch.stack(feats[1:]))
+        for gather in (False, True):
+            if C == 48:
+                gref, gsrc = ops.warp_corr_init_bwd(ref_f, src_f, rt, disp_min, disp_max, dev(ops, rnd(B, S, 4, 7, H, W, seed=121)), gather=gather)
+            else:
+                gref, gsrc = ops.getcost_bwd(ref_f, src_f, rt, dev(ops, rnd(B, 1, H, W, seed=122, lo=0, hi=1)), None,
+                                             dev(ops, rnd(B, S, H // 2, W // 2, seed=123, lo=0.05, hi=1)), disp_min, disp_max, 6, 2.0 / 384,
+                                             0.25, 4.0, 1, dev(ops, rnd(B, 24, H, W, seed=124)), gather=gather)
+            assert torch.isfinite(gref).all() and float(gsrc[0].abs().max()) > 0
+            assert torch.equal(gsrc[1].cpu(), torch.zeros(B, H, W, C))
+
+
+@pytest.mark.parametrize("D", [256, 257])
+def test_warp_corr_init_backward_depth_count_boundary(ops, D, monkeypatch):
+    """D <= 256 is where gather=False stops taking the window kernel (its depth table holds 256 planes).  D = 257 must be the per-pixel
+    kernel: the same grad_ref bit for bit as gather=True (registers, no atomics); at D = 256 the window kernel's grad_ref, summed in
+    another order, differs in the last bits (an observable of today's summation orders, see the assertion).  Both against fp64."""
+    B, S, C, H, W = 2, 1, 48, 6, 10
+    pm = _cams_bwd("cams", B, S + 1, H, W)
+    feats = [rnd(B, C, H, W, seed=130 + v) for v in range(S + 1)]
+    disp_min, disp_max = _disp_range(B)
+    case = dict(c=_WIB("cams", D, H, W, H, W, S, None), pm=pm, feats=feats, disp_min=disp_min, disp_max=disp_max,
+                gcor=rnd(B, S, 4, D, H, W, seed=131), ref={})
+    monkeypatch.setattr(ops, "debug_fill", float("nan"))
+    monkeypatch.setitem(ops.tune, "bwd_il", False)
+    rt, gref, gsrc = _sweep_bwd_run(ops, case, False)
+    _, gref_g, gsrc_g = _sweep_bwd_run(ops, case, True)
+    ref = _sweep_bwd_ref(case, rt)
+    for what, gr, gs in (("gather=False", gref, gsrc), ("gather=True", gref_g, gsrc_g)):
+        _warp_check(f"warp_corr_init_bwd D={D} {what} gref", gr, ref.grads[0], ref.floor)
+        _warp_check(f"warp_corr_init_bwd D={D} {what} gsrc", gs[0], ref.grads[1], ref.floor)
+    same = torch.equal(gref.cpu(), gref_g.cpu())
+    if D > 256:
+        assert same, "gather=False at D = 257 did not run the per-pixel kernel: grad_ref differs from gather=True"
+    else:
+        # a dispatch observable only as long as the two kernels sum in different orders (the window kernel folds the planes that share
+        # a footprint into tap weights first); both results are held to fp64 above whichever kernel ran
+        assert not same, ("grad_ref at D = 256 equals the per-pixel kernel's bit for bit: either gather=False no longer takes the window "
+                          "kernel at D = 256, or the two kernels' summation orders now coincide (then this observable needs replacing, "
+                          "no bug)")
 
 
 @pytest.mark.parametrize("cin,cout,k,stride,pad,in_mode", [
