@@ -79,6 +79,19 @@ def conv1_pair_applies(o: Ops, c1):
             o.conv1_pair_supported(c1) and c1.shape[3] >= K.Ops.CONV1_PAIR_STRIP)
 
 
+# On: 3.72 against 4.52 ms per 576 images for the two launches (tools/conv_bench.py row); the step 0.6-0.9 ms shorter in three interleaved rounds,
+# every fused run ahead of every other run (profiles/fpn_tail_step_ab.json); DMVS_FPN_TAIL=0 turns it off
+FPN_TAIL_DEFAULT = "1"
+
+
+def fpn_tail_applies(o: Ops, f, c2, c3, layout, feat_dtype):
+    """inner1 + the upsample-add + out2 run as one kernel (Ops.fpn_tail) under conv_arith = "split" -- out2 computes in split arithmetic only
+    there, and the kernel gives the two launches' bits -- for channel-last fp32 features, when the sum has no other reader (no out3: DiffMVS)
+    and the geometry applies; DMVS_FPN_TAIL=0 is the A/B knob: the two launches"""
+    return (o.conv_arith == K.ARITH_SPLIT and layout == K.LAYOUT_NHWC and feat_dtype == torch.float32 and "out3" not in f and
+            os.environ.get("DMVS_FPN_TAIL", FPN_TAIL_DEFAULT) != "0" and o.fpn_tail_supported(c2, c3))
+
+
 def run_feature(o: Ops, f, x, layout=K.LAYOUT_NHWC, feat_dtype=torch.float32):
     """x [N,3,H,W] -> {'stage1': [N,H/8,W/8,48], 'stage2': [N,H/4,W/4,32], ('stage3': [N,H/2,W/2,16])} (NHWC by
     default: the layout the warp kernels read; feat_dtype bf16 / fp16 = reduced-precision feature storage, rounded in the
@@ -96,6 +109,9 @@ def run_feature(o: Ops, f, x, layout=K.LAYOUT_NHWC, feat_dtype=torch.float32):
     c2 = o.conv2d(f["conv2.2"], o.conv2d(f["conv2.1"], o.conv2d(f["conv2.0"], c1, act=R), act=R), act=R)
     c3 = o.conv2d(f["conv3.2"], o.conv2d(f["conv3.1"], o.conv2d(f["conv3.0"], c2, act=R), act=R), act=R)
     out = {"stage1": o.conv2d(f["out1"], c3, out_layout=layout, out_dtype=feat_dtype)}
+    if fpn_tail_applies(o, f, c2, c3, layout, feat_dtype):
+        out["stage2"] = o.fpn_tail(f["inner1"], f["out2"], c2, c3)      # inner1 + upsample-add + out2: the sum has no other reader, it stays in LDS
+        return out
     intra = o.conv2d(f["inner1"], c2, residual=c3, res_mode=K.IN_UPSAMPLE2)
     out["stage2"] = o.conv2d(f["out2"], intra, out_layout=layout, out_dtype=feat_dtype)
     if "out3" in f:

@@ -433,6 +433,36 @@ class Ops:
                    _ptr(split_weights(pc2)), _ptr(pc2.scale), _ptr(pc2.shift), _ptr(y), N, H, W, tune, self.stream())
         return y
 
+    FPN_TAIL_STRIP, FPN_TAIL_SEGMENT = 32, 64      # csrc/fpn_tail.hip: a work unit's output columns / rows (US, UR)
+
+    @staticmethod
+    def fpn_tail_supported(c2, c3):
+        """geometry of dmvs_featurenet_fpn_tail_f32: 32 and 64 channels, c3 at half the resolution, even H, c3 rows of whole 16-byte pieces
+        (W % 8 == 0) on 16-byte aligned contiguous fp32 tensors, 32-bit offsets inside an image"""
+        if not (c2.dim() == 4 and c3.dim() == 4 and c2.dtype == torch.float32 and c3.dtype == torch.float32):
+            return False
+        N, C, H, W = c2.shape
+        return (C == 32 and H % 2 == 0 and W % 8 == 0 and H > 0 and W > 0 and tuple(c3.shape) == (N, 64, H // 2, W // 2) and
+                64 * H * W < 2 ** 31 and c2.is_contiguous() and c3.is_contiguous() and c2.data_ptr() % 16 == 0 and c3.data_ptr() % 16 == 0)
+
+    def fpn_tail(self, pc_inner: PackedConv, pc_out: PackedConv, c2, c3, tune=0):
+        """out2(inner1(c2) + nearest_up2(c3)) of FeatureNet in one kernel: c2 [N,32,H,W], c3 [N,64,H/2,W/2] -> [N,H,W,32] channel-last fp32, the
+        1x1 in exact fp32 and the 3x3 in split-bf16 arithmetic: the bits of conv2d(pc_out, conv2d(pc_inner, c2, residual=c3,
+        res_mode=IN_UPSAMPLE2), out_layout=LAYOUT_NHWC) under ARITH_SPLIT.  tune: 1 .. 65535 forces the grid."""
+        self._chk(c2, c3)
+        if not (pc_inner.cin == 32 and pc_inner.cout == 64 and pc_inner.cout_pad == 64 and pc_inner.k == (1, 1) and pc_inner.stride == 1 and
+                pc_inner.pad == (0, 0) and pc_inner.scale is None and pc_out.cin == 64 and pc_out.cout == 32 and pc_out.cout_pad == 32 and
+                pc_out.k == (3, 3) and pc_out.stride == 1 and pc_out.pad == (1, 1) and pc_out.scale is None and pc_out.shift is None):
+            raise _lib.DmvsError("fpn_tail: expects FeatureNet's inner1 (32->64 1x1, bias) and out2 (64->32 3x3, no bias)")
+        if not self.fpn_tail_supported(c2, c3):
+            raise _lib.DmvsError(f"fpn_tail: needs c2 [N,32,H,W] and c3 [N,64,H/2,W/2] with even H, W % 8 == 0, contiguous and 16-byte aligned, "
+                                 f"got {tuple(c2.shape)} and {tuple(c3.shape)}")
+        N, _, H, W = c2.shape
+        y = self.empty(N, H, W, 32)
+        self._call("dmvs_featurenet_fpn_tail_f32", _ptr(c2), _ptr(c3), _ptr(pc_inner.weight), _ptr(pc_inner.shift), _ptr(split_weights(pc_out)),
+                   _ptr(y), N, H, W, tune, self.stream())
+        return y
+
     def conv2d_wgrad(self, pc: PackedConv, x0, grad_out, x1=None, *, mul0=None, in_mode=IN_PLAIN, want_bias=False, tune=None,
                      into_gw=None, into_gb=None):
         """Weight gradient of conv2d(pc, x0, x1, mul0=..., in_mode=...) in torch layout [cout, cin, kh, kw]

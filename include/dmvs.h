@@ -186,6 +186,20 @@ int dmvs_featurenet_conv1_pair_f32(const float* x, const void* wsplit1, const fl
                                    const float* scale2, const float* shift2, float* y, int32_t N, int32_t H, int32_t W, int32_t tune,
                                    void* stream);
 
+/* FeatureNet's FPN tail for stage 2 in one kernel: y = conv3x3(conv1x1(c2) + bias + nearest_up2(c3)) with 32 -> 64 -> 32 channels, the 3x3 with
+ * zero padding and no bias / BN / activation (models/module.py:409-411 inner1, out2); the 64-channel sum never leaves LDS (a workgroup marches
+ * down a strip of 32 output columns over a four-row ring of bf16 triples).  For networks without an out3: nothing else reads the sum there.
+ *   c2 [N,32,H,W], c3 [N,64,H/2,W/2] NCHW;  y [N,H,W,32] channel-last;  w_inner [32][64] = the 1x1 layer's packed weights [cin][cout],
+ *   b_inner [64] (NULL = 0);  wsplit_out = the 3x3 layer's weights as dmvs_conv2d_desc.weight_split lays them out (cout_pad = 32:
+ *   [8 chunks][3 tap groups][3 planes][4][32][8] bf16; an output-channel permutation such as NHWC-g4 is a permutation of these weights).
+ * Arithmetic: the 1x1 in exact fp32, the 3x3 in DMVS_ARITH_SPLIT, the same matrix instructions on the same operands in the same order as the two
+ * dmvs_conv2d_f32 launches (residual = c3, res_mode = DMVS_IN_UPSAMPLE2; then out_layout = DMVS_LAYOUT_NHWC, arith = DMVS_ARITH_SPLIT): the
+ * same bits.  Every output depends only on its position in the image (not on N, the grid or the unit a pixel falls into).
+ * DMVS_EINVAL unless H is even, W a multiple of 8, c2 / c3 / y / wsplit_out are 16-byte aligned and 64*H*W < 2^31.
+ * tune: 0 = the grid of the occupancy query; 1 .. 65535 = that many workgroups (tests). */
+int dmvs_featurenet_fpn_tail_f32(const float* c2, const float* c3, const float* w_inner, const float* b_inner, const void* wsplit_out,
+                                 float* y, int32_t N, int32_t H, int32_t W, int32_t tune, void* stream);
+
 /* Weight (and bias) gradient of the convolution described by `d` (its input side: in0 / in1 / mul0 / in_mode / kh /
  * kw / stride / pad / cout / cout_pad / B / Hin / Win / Hout / Wout; epilogue fields are ignored; in0 / in1 / mul0 must be DENSE tensors:
  * DMVS_EINVAL when in0_cstride, gate_cstride or out_mul is set):

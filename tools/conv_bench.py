@@ -106,6 +106,36 @@ def main():
         del x
         if only:
             return
+    tail_row = "feat inner1 + out2 tail N576"
+    if not only or ("tail" in only and only in tail_row):
+        # inner1 + upsample-add + out2 of the 576-image headline step: the one-kernel FPN tail (Ops.fpn_tail) against the two launches it
+        # replaces (exact-fp32 1x1 with the nearest-x2 residual, split 3x3 with channel-last output), alternating rounds, median per form
+        so = o.with_conv_arith(K.ARITH_SPLIT)
+        c2 = torch.randn(576, 32, 128, 160, generator=g, device="cuda").relu_()
+        c3 = torch.randn(576, 64, 64, 80, generator=g, device="cuda").relu_()
+        pci = K.pack_conv2d(torch.randn(64, 32, 1, 1, generator=g, device="cuda") * 0.1, torch.rand(64, generator=g, device="cuda"))
+        pco = K.pack_conv2d(torch.randn(32, 64, 3, 3, generator=g, device="cuda") * 0.1, None, stride=1, pad=(1, 1))
+        forms = [lambda: so.fpn_tail(pci, pco, c2, c3),
+                 lambda: so.conv2d(pco, so.conv2d(pci, c2, residual=c3, res_mode=K.IN_UPSAMPLE2), out_layout=K.LAYOUT_NHWC)]
+        equal = bool(torch.equal(forms[0](), forms[1]()))
+        times = [[], []]
+        for _ in range(5):
+            for f, ts in zip(forms, times):
+                f()
+                st, en = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                st.record()
+                for _ in range(5):
+                    f()
+                en.record()
+                torch.cuda.synchronize()
+                ts.append(st.elapsed_time(en) * 200.0)
+        us_tail, us_two = sorted(times[0])[2], sorted(times[1])[2]
+        print(json.dumps({"layer": tail_row, "us_tail": round(us_tail, 1), "us_two_launches": round(us_two, 1),
+                          "ratio": round(us_tail / us_two, 4), "equal": equal, "tail_runs": [round(t, 1) for t in times[0]],
+                          "two_runs": [round(t, 1) for t in times[1]]}), flush=True)
+        del c2, c3
+        if only:
+            return
     for name, N, cin, cout, k, s, H, W in SHAPES:
         if only and only not in name:
             continue
