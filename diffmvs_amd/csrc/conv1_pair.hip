@@ -35,7 +35,7 @@
 // each, no tail.  (R = 128 halves the warm-up but leaves 9 units per workgroup; R = 256 leaves 4.5: a 10 % tail.)
 
 #include "dmvs_common.h"
-#include "dmvs_bf16.h"
+#include "dmvs_ring.h"
 #include "dmvs_lds_poison.h"
 
 namespace {
@@ -46,23 +46,15 @@ typedef uint32_t u32x4s __attribute__((ext_vector_type(4)));
 constexpr int PB = 512;                     // threads per workgroup: waves 0-3 conv1.1, waves 4-7 conv1.2
 constexpr int US = 80, UR = 64;             // a unit's output columns / rows
 constexpr int NP = US + 4;                  // ring positions per row: input columns X0 - 2 .. X0 + 81 (mid: X0 - 1 .. X0 + 80 in positions 0 .. 81)
-constexpr int SLOTS = 4;
-constexpr int PLQ = SLOTS * 2 * NP;         // 16-byte entries of one bf16 plane: [slot][chunk][position]
-constexpr int RINGQ = 3 * PLQ;              // a ring: 32,256 bytes
+typedef dmvs_ring<2, NP> Ring;              // two chunks of 8 channels: 32,256 bytes
+constexpr int PLQ = Ring::PLQ, RINGQ = Ring::RINGQ;
 constexpr int NLOAD = 2 * 2 * NP;           // conversion items of a step: (row of the pair, chunk, position)
 constexpr int SW = US + 8;                  // fp32 staging row: the 16-byte aligned cover of columns X0 - 2 .. X0 + 81 = columns X0 - 4 .. X0 + 83
 constexpr int STAGEF = 2 * 16 * SW;         // staging buffer [2 rows][16 channels][88]: 704 16-byte pieces, 11,264 bytes
 constexpr int NPIECE = STAGEF / 4;
 
-__device__ __attribute__((aligned(16))) const float conv1_pair_zero16[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-#define DMVS_LDS_P(p) ((__attribute__((address_space(3))) void*)(p))
-// Opaque redefinition of a lane coordinate at the top of every step (conv2d_tiled.h, the tile-walking form): without it hipcc hoists every
-// lane-dependent address of the step -- staging pieces, conversion items, operand positions -- out of the step loop, keeps them all live and spills
-#ifdef DMVS_HOST_EMULATION
-#define DMVS_OPAQUE(v) ((void)0)
-#else
-#define DMVS_OPAQUE(v) asm volatile("" : "+v"(v))
-#endif
+// (DMVS_OPAQUE at the top of every step: left alone hipcc hoists every lane-dependent address of the step -- staging pieces, conversion items,
+// operand positions -- out of the step loop, keeps them all live and spills)
 
 __global__ void __launch_bounds__(PB) __attribute__((amdgpu_waves_per_eu(4, 4)))      // two workgroups per CU (LDS): at most 128 registers
 featurenet_conv1_pair_kernel(const float* __restrict__ x, const u32x4s* __restrict__ ws1, const float* __restrict__ scale1,
@@ -91,12 +83,9 @@ featurenet_conv1_pair_kernel(const float* __restrict__ x, const u32x4s* __restri
     const float* const scp = role ? scale2 : scale1;
     const float* const shp = role ? shift2 : shift1;
     const float sc = scp ? scp[m] : 1.0f, sh = shp ? shp[m] : 0.0f;
-    int taps = 0;       // (ky | kx << 2) of tap group g in bits 4g .. 4g + 3
+    int taps = 0;       // (ky | kx << 2) of tap group g in bits 4g .. 4g + 3: dmvs_ring::operand
 #pragma unroll
-    for (int g = 0; g < 3; ++g) {
-        const int t = min(4 * g + kq, 8);      // (a tap slot beyond the kernel meets zero weights)
-        taps |= ((t / 3) | ((t % 3) << 2)) << (4 * g);
-    }
+    for (int g = 0; g < 3; ++g) taps |= dmvs_tap_slot<3, 3, 2>(g, kq) << (4 * g);
     const u32x4s* const src = reinterpret_cast<const u32x4s*>(lds) + role * RINGQ;      // the ring this wave's layer reads
     u32x4s* const in_q = reinterpret_cast<u32x4s*>(lds);
     uint16_t* const mid_h = reinterpret_cast<uint16_t*>(lds) + RINGQ * 8;
@@ -107,11 +96,8 @@ featurenet_conv1_pair_kernel(const float* __restrict__ x, const u32x4s* __restri
     int lm = m, ltb = tb;              // (redefined opaquely per step)
 
     for (int unit = blockIdx.x; unit < nunits; unit += gridDim.x) {
-        const int sx = unit % nsx;
-        const int uq = unit / nsx;
-        const int sy = uq % nsy, n = uq / nsy;
-        const int X0 = US * sx, Y0 = UR * sy;
-        const int Yend = min(Y0 + UR, H) - 1;
+        const dmvs_unit u(unit, nsx, nsy, US, UR, H);
+        const int n = u.n, X0 = u.X0, Y0 = u.Y0, Yend = u.Yend;
         const int nsteps = ((Yend - Y0 + 2) >> 1) + 4;
         const float* const xb = x + (long)n * 16 * plane;
         float* const yb = y + (long)n * 16 * plane;
@@ -126,12 +112,7 @@ featurenet_conv1_pair_kernel(const float* __restrict__ x, const u32x4s* __restri
             // the fourth, hi (live to the sixth) into a second quad -- 16 operand registers.  (Left alone the scheduler reuses one quad per plane and waits
             // out the LDS latency twice per tap group; all three planes double-buffered are 24 registers, and the kernel spills.)
             bf16x8 ph[2], pm, pl;
-            auto qp_of = [&](int s) {
-                const int c = s / 3, g = s - c * 3;
-                const int tg = taps >> (4 * g);
-                const int slot = (row + 3 + (tg & 3)) & 3;              // source row row - 1 + ky
-                return (slot * 2 + c) * NP + p + ((tg >> 2) & 3);
-            };
+            auto qp_of = [&](int s) { return Ring::operand(s, taps, row, p); };
             {
                 const int qp = qp_of(0);
                 pl = __builtin_bit_cast(bf16x8, src[2 * PLQ + qp]);
@@ -146,7 +127,7 @@ featurenet_conv1_pair_kernel(const float* __restrict__ x, const u32x4s* __restri
                 const bf16x8 wh = __builtin_bit_cast(bf16x8, wq[c][g][0]), wm = __builtin_bit_cast(bf16x8, wq[c][g][1]),
                              wl = __builtin_bit_cast(bf16x8, wq[c][g][2]);
                 __builtin_amdgcn_sched_barrier(0);
-                a = dmvs_mfma_bf16(pl, wh, a);      // smallest partial products first
+                a = dmvs_mfma_bf16(pl, wh, a);      // the six partial products in the order of dmvs_split_step (dmvs_bf16.h)
                 __builtin_amdgcn_sched_barrier(0);
                 if (s + 1 < 6) pl = __builtin_bit_cast(bf16x8, src[2 * PLQ + qn]);
                 __builtin_amdgcn_sched_barrier(0);
@@ -176,16 +157,9 @@ featurenet_conv1_pair_kernel(const float* __restrict__ x, const u32x4s* __restri
                 DMVS_OPAQUE(ltb);
 #pragma unroll
                 for (int k = 0; k < 3; ++k) {
-                    const int e = k * (PB / 2) + ltb;
-                    if (k * (PB / 2) + wr * 64 < NPIECE) {       // (wave-uniform: 704 pieces = 11 waves' worth)
-                        const int li = e / (NPIECE / 2), rem = e - li * (NPIECE / 2);
-                        const int ch = rem / (SW / 4), pc = rem - ch * (SW / 4);
-                        const int row = lrow0 + li, col = X0 - 4 + 4 * pc;
-                        const bool ok = row <= Yend + 2 && row >= 0 && row < H && col >= 0 && col < W;
-                        const float* srcp = ok ? xb + (ch * iplane + row * W + col) : conv1_pair_zero16;
-                        float* dstp = stage + (k * (PB / 2) + wr * 64) * 4;
-                        __builtin_amdgcn_global_load_lds(srcp, DMVS_LDS_P(dstp), 16, 0, 0);
-                    }
+                    if (k * (PB / 2) + wr * 64 < NPIECE)       // (wave-uniform: 704 pieces = 11 waves' worth)
+                        dmvs_stage_piece<2, 16, SW>(xb, iplane, H, W, lrow0, X0 - 4, lrow0 + (k * (PB / 2) + ltb) / (NPIECE / 2) <= Yend + 2,
+                                                    k * (PB / 2) + ltb, stage + (k * (PB / 2) + wr * 64) * 4);
                 }
                 const int rowbase = Y0 + 2 * j - 8;
                 f32x4 acc[3];
@@ -222,7 +196,7 @@ featurenet_conv1_pair_kernel(const float* __restrict__ x, const u32x4s* __restri
                         for (int c8 = 0; c8 < 8; ++c8) v[c8] = sp[c8 * SW];
                         bf16x8 h8, m8, l8;
                         dmvs_split3_bf16x8(v, h8, m8, l8);
-                        u32x4s* const d = in_q + (((lrow + 4) & 3) * 2 + lc) * NP + lq;
+                        u32x4s* const d = in_q + Ring::index(lrow, lc, lq);
                         d[0] = __builtin_bit_cast(u32x4s, h8);
                         d[PLQ] = __builtin_bit_cast(u32x4s, m8);
                         d[2 * PLQ] = __builtin_bit_cast(u32x4s, l8);
@@ -270,7 +244,7 @@ featurenet_conv1_pair_kernel(const float* __restrict__ x, const u32x4s* __restri
                         }
                         bf16x8 h8, m8, l8;
                         dmvs_split3_bf16x8(v, h8, m8, l8);
-                        uint16_t* const d = mid_h + ((((row + 4) & 3) * 2 + (m >> 3)) * NP + p0) * 8 + (m & 7);
+                        uint16_t* const d = mid_h + Ring::index(row, m >> 3, p0) * 8 + (m & 7);
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
                             if (p0 + r < US + 2) {
@@ -287,19 +261,6 @@ featurenet_conv1_pair_kernel(const float* __restrict__ x, const u32x4s* __restri
     }
 }
 
-#ifdef DMVS_HOST_EMULATION
-int conv1_pair_resident() { return 2; }
-#else
-int conv1_pair_resident() {
-    int dev = 0, per_cu = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 512;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(featurenet_conv1_pair_kernel), PB, 0) != hipSuccess || per_cu < 1)
-        per_cu = 1;
-    return per_cu * prop.multiProcessorCount;
-}
-#endif
-
 }  // namespace
 
 extern "C" int dmvs_featurenet_conv1_pair_f32(const float* x, const void* wsplit1, const float* scale1, const float* shift1, const void* wsplit2,
@@ -313,10 +274,8 @@ extern "C" int dmvs_featurenet_conv1_pair_f32(const float* x, const void* wsplit
     const long nunits = (long)nsx * nsy * N;
     if (nunits >= (1L << 31)) return DMVS_EINVAL;
     // persistent workgroups: as many as are resident at once; tune & 0xffff forces the grid (tests: results do not depend on it)
-    static const int resident = conv1_pair_resident();
-    long grid = (tune & 0xffff) ? (tune & 0xffff) : resident;
-    if (grid > nunits) grid = nunits;
-    hipLaunchKernelGGL(featurenet_conv1_pair_kernel, dim3((unsigned)grid), dim3(PB), 0, (hipStream_t)stream, x,
+    static const int resident = dmvs_resident_workgroups(reinterpret_cast<const void*>(featurenet_conv1_pair_kernel), PB);
+    hipLaunchKernelGGL(featurenet_conv1_pair_kernel, dim3(dmvs_persistent_grid(tune, resident, nunits)), dim3(PB), 0, (hipStream_t)stream, x,
                        reinterpret_cast<const u32x4s*>(wsplit1), scale1, shift1, reinterpret_cast<const u32x4s*>(wsplit2), scale2, shift2, y, N, H, W,
                        nsx, nsy);
     return dmvs_launch_status();

@@ -346,8 +346,8 @@ __global__ void __launch_bounds__(DMVS_BLOCK) conv2d_wgrad_kernel(const dmvs_con
                 else if (halfres) off = cig * plane0 + (iy >> 1) * pW + (ix >> 1);
                 else off = (cig >> 2) * plane0 + (iy * 2 + ((cig >> 1) & 1)) * pW + ix * 2 + (cig & 1);
                 const float* src = !ok ? dmvs_zero16 : (cig < d.c0 ? in0b + off : in1b + ((cig - d.c0) * plane1 + iy * d.Win + ix));
-                if constexpr (V16) __builtin_amdgcn_global_load_lds(src, DMVS_LDS(s_in + (i * DMVS_BLOCK + wave * 64) * 4), 16, 0, 0);
-                else __builtin_amdgcn_global_load_lds(src, DMVS_LDS(s_in + i * DMVS_BLOCK + wave * 64), 4, 0, 0);
+                if constexpr (V16) __builtin_amdgcn_global_load_lds(src, DMVS_LDS_PTR(s_in + (i * DMVS_BLOCK + wave * 64) * 4), 16, 0, 0);
+                else __builtin_amdgcn_global_load_lds(src, DMVS_LDS_PTR(s_in + i * DMVS_BLOCK + wave * 64), 4, 0, 0);
             }
         }
 #pragma unroll
@@ -356,8 +356,8 @@ __global__ void __launch_bounds__(DMVS_BLOCK) conv2d_wgrad_kernel(const dmvs_con
                 const int p = g_pp[i];
                 const bool ok = p >= 0 && oy0 + (p >> 4) < d.Hout && ox0 + (p & 15) < d.Wout;
                 const float* src = ok ? gb + g_off[i] : dmvs_zero16;
-                if constexpr (V16) __builtin_amdgcn_global_load_lds(src, DMVS_LDS(s_g + (i * DMVS_BLOCK + wave * 64) * 4), 16, 0, 0);
-                else __builtin_amdgcn_global_load_lds(src, DMVS_LDS(s_g + i * DMVS_BLOCK + wave * 64), 4, 0, 0);
+                if constexpr (V16) __builtin_amdgcn_global_load_lds(src, DMVS_LDS_PTR(s_g + (i * DMVS_BLOCK + wave * 64) * 4), 16, 0, 0);
+                else __builtin_amdgcn_global_load_lds(src, DMVS_LDS_PTR(s_g + i * DMVS_BLOCK + wave * 64), 4, 0, 0);
             }
         }
         DMVS_DMA_BARRIER();

@@ -21,11 +21,6 @@ constexpr int pad16mod32(int n) {   // smallest m >= n with m % 32 == 16
     return m;
 }
 
-// all-zero source for LDS-DMA lanes that stage padding (an LDS-DMA lane cannot write a literal)
-__device__ __attribute__((aligned(16))) const float dmvs_zero16[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-
-#define DMVS_LDS(p) ((__attribute__((address_space(3))) void*)(p))
-
 template <int KH, int KW, int S, int NT, int MT, int AR = DMVS_ARITH_F32, int WX = 1, bool V16 = false>
 struct ConvCfg {
     static constexpr int T = KH * KW;
@@ -289,10 +284,10 @@ __global__ void __launch_bounds__(DMVS_BLOCK, conv_min_waves(NT, MT, AR)) conv2d
                         const float* srcp = cb + (unsigned)p_sp[it];
                         if constexpr (V16) {
                             float* dstp = buf + ci * PLANE + (it * DMVS_BLOCK + wave * 64) * 4;
-                            __builtin_amdgcn_global_load_lds(srcp, DMVS_LDS(dstp), 16, 0, 0);
+                            __builtin_amdgcn_global_load_lds(srcp, DMVS_LDS_PTR(dstp), 16, 0, 0);
                         } else {
                             float* dstp = buf + ci * PLANE + it * DMVS_BLOCK + wave * 64;
-                            __builtin_amdgcn_global_load_lds(srcp, DMVS_LDS(dstp), 4, 0, 0);
+                            __builtin_amdgcn_global_load_lds(srcp, DMVS_LDS_PTR(dstp), 4, 0, 0);
                         }
                     }
                 }
@@ -307,7 +302,7 @@ __global__ void __launch_bounds__(DMVS_BLOCK, conv_min_waves(NT, MT, AR)) conv2d
                 const int cw = c0 + w_ci[i];
                 const float* srcp = (w_off[i] >= 0 && cw < cin) ? d.weight + (cw * T * d.cout_pad + w_off[i]) : dmvs_zero16;
                 float* dstp = wbuf + (i * DMVS_BLOCK + wave * 64) * 4;
-                __builtin_amdgcn_global_load_lds(srcp, DMVS_LDS(dstp), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds(srcp, DMVS_LDS_PTR(dstp), 16, 0, 0);
             }
         }
     };
@@ -341,9 +336,9 @@ __global__ void __launch_bounds__(DMVS_BLOCK, conv_min_waves(NT, MT, AR)) conv2d
     if constexpr (WALK) {
         // Opaque redefinition of the lane coordinates: without it hipcc hoists every lane-dependent address of the chunk loop and
         // the epilogue out of the tile loop and keeps them all live (112 instead of 63 VGPRs, 3 instead of 5 waves per SIMD)
-#ifndef DMVS_HOST_EMULATION
-        asm volatile("" : "+v"(m), "+v"(kq), "+v"(tid));
-#endif
+        DMVS_OPAQUE(m);
+        DMVS_OPAQUE(kq);
+        DMVS_OPAQUE(tid);
     }
     const int b = s_b, ox0 = s_ox0, oy0 = s_oy0;
     f32x4 acc[MT][NT];

@@ -47,10 +47,6 @@ constexpr int pad16mod32_3d(int n) {
     return m;
 }
 
-// all-zero source for LDS-DMA lanes that stage padding
-__device__ __attribute__((aligned(16))) const float dmvs_zero16_3d[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-#define DMVS_LDS(p) ((__attribute__((address_space(3))) void*)(p))
-
 // ---- staging and epilogue pieces shared by the matrix-core kernels -------------------------------------------------
 // Halo tiles go HBM/L2 -> LDS by LDS-DMA, 4 bytes per lane (their rows are not 16-byte multiples).  Which (z, y, x) of
 // a channel plane of the halo tile a lane's elements are never changes, so it is decoded ONCE per workgroup; per tile
@@ -91,9 +87,9 @@ struct HaloMap {
             if (zyx[it] >= 0) {
                 const unsigned z = (unsigned)zyx[it];
                 const bool in = chan_live && ((((z | kHaloGuard) - lo) & (him1 - z) & kHaloGuard) == kHaloGuard);
-                const float* srcp = in ? origin + off[it] : dmvs_zero16_3d;
+                const float* srcp = in ? origin + off[it] : dmvs_zero16;
                 float* dstp = dst_plane + it * DMVS_BLOCK + wave * 64;
-                __builtin_amdgcn_global_load_lds(srcp, DMVS_LDS(dstp), 4, 0, 0);
+                __builtin_amdgcn_global_load_lds(srcp, DMVS_LDS_PTR(dstp), 4, 0, 0);
             }
         }
     }
@@ -139,9 +135,9 @@ struct HaloMap16 {
             if (zyx[it] >= 0) {
                 const unsigned z = (unsigned)zyx[it];
                 const bool in = chan_live && ((((z | kHaloGuard) - lo) & (him1 - z) & kHaloGuard) == kHaloGuard);
-                const float* srcp = in ? origin + off[it] : dmvs_zero16_3d;
+                const float* srcp = in ? origin + off[it] : dmvs_zero16;
                 float* dstp = dst_plane + (it * DMVS_BLOCK + wave * 64) * 4;
-                __builtin_amdgcn_global_load_lds(srcp, DMVS_LDS(dstp), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds(srcp, DMVS_LDS_PTR(dstp), 16, 0, 0);
             }
         }
     }
@@ -199,9 +195,9 @@ struct SlabMap {
         for (int i = 0; i < W_IT; ++i) {
             if (ci[i] >= 0) {
                 const int cw = c0 + ci[i];
-                const float* srcp = (off[i] >= 0 && cw < cin) ? weight + (cw * 27 * cout_pad + off[i]) : dmvs_zero16_3d;
+                const float* srcp = (off[i] >= 0 && cw < cin) ? weight + (cw * 27 * cout_pad + off[i]) : dmvs_zero16;
                 float* dstp = wbuf + (i * DMVS_BLOCK + wave * 64) * 4;
-                __builtin_amdgcn_global_load_lds(srcp, DMVS_LDS(dstp), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds(srcp, DMVS_LDS_PTR(dstp), 16, 0, 0);
             }
         }
     }
@@ -821,9 +817,9 @@ __global__ void __launch_bounds__(DMVS_BLOCK) conv3d_c1_rows_kernel(const dmvs_c
 #pragma unroll
         for (int it = 0; it < kC1RowsPieces; ++it) {
             if (off[it] != -2) {
-                const float* srcp = off[it] >= 0 ? base + off[it] : dmvs_zero16_3d;
+                const float* srcp = off[it] >= 0 ? base + off[it] : dmvs_zero16;
                 float* dstp = buf + (it * DMVS_BLOCK + wave * 64) * 4;
-                __builtin_amdgcn_global_load_lds(srcp, DMVS_LDS(dstp), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds(srcp, DMVS_LDS_PTR(dstp), 16, 0, 0);
             }
         }
     };
@@ -1308,8 +1304,8 @@ __global__ void __launch_bounds__(DMVS_BLOCK) conv3d_wgrad_kernel(const dmvs_con
                 const int gd = d0 * S - 1 + zz, gy = y0 * S - 1 + yy, gx = x0 * S - 1 + xx;
                 const bool ok = rem < ID * IH * IW && c0 + ci < d.cin && gd >= 0 && gd < d.Din && gy >= 0 && gy < d.Hin &&
                                 gx >= 0 && gx < d.Win;
-                const float* src = ok ? inb + ((c0 + ci) * vol + (gd * d.Hin + gy) * d.Win + gx) : dmvs_zero16_3d;
-                __builtin_amdgcn_global_load_lds(src, DMVS_LDS(s_in + i * DMVS_BLOCK + wave * 64), 4, 0, 0);
+                const float* src = ok ? inb + ((c0 + ci) * vol + (gd * d.Hin + gy) * d.Win + gx) : dmvs_zero16;
+                __builtin_amdgcn_global_load_lds(src, DMVS_LDS_PTR(s_in + i * DMVS_BLOCK + wave * 64), 4, 0, 0);
             }
         }
 #pragma unroll 2
@@ -1319,8 +1315,8 @@ __global__ void __launch_bounds__(DMVS_BLOCK) conv3d_wgrad_kernel(const dmvs_con
                 const int co = e / GROW, p = e - co * GROW;
                 const int od = d0 + (p >> 6), oy = y0 + ((p >> 4) & 3), ox = x0 + (p & 15);
                 const bool ok = p < 256 && cobase + co < d.cout && od < d.Dout && oy < d.Hout && ox < d.Wout;
-                const float* src = ok ? gb + ((size_t)(cobase + co) * ovol + ((size_t)od * d.Hout + oy) * d.Wout + ox) : dmvs_zero16_3d;
-                __builtin_amdgcn_global_load_lds(src, DMVS_LDS(s_g + i * DMVS_BLOCK + wave * 64), 4, 0, 0);
+                const float* src = ok ? gb + ((size_t)(cobase + co) * ovol + ((size_t)od * d.Hout + oy) * d.Wout + ox) : dmvs_zero16;
+                __builtin_amdgcn_global_load_lds(src, DMVS_LDS_PTR(s_g + i * DMVS_BLOCK + wave * 64), 4, 0, 0);
             }
         }
         DMVS_DMA_BARRIER();

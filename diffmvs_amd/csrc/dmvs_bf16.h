@@ -1,5 +1,6 @@
-// bf16 matrix-core helpers shared by the 2-D convolutions (conv2d_tiled.h) and the fused FeatureNet stem (stem.hip): the operand type of
-// v_mfma_f32_16x16x32_bf16, round-to-nearest conversions, and the three-way split of fp32 values behind DMVS_ARITH_SPLIT.
+// bf16 matrix-core helpers shared by the 2-D convolutions (conv2d_tiled.h) and the fused FeatureNet kernels (dmvs_ring.h): the operand type of
+// v_mfma_f32_16x16x32_bf16, round-to-nearest conversions, the three-way split of fp32 values behind DMVS_ARITH_SPLIT, and one K = 32 step of
+// a split product.
 #pragma once
 #include "dmvs_common.h"
 
@@ -58,3 +59,36 @@ __device__ __forceinline__ void dmvs_split3_bf16x8(const float (&v)[8], bf16x8& 
     l = dmvs_pack_bf16x8(r2);
 }
 
+// One K = 32 step of a split product, for NG independent accumulators that share the weight operand: THE ORDER of the six partial products
+// (pixel part * weight part), smallest first: lo*hi, hi*lo, mid*mid, mid*hi, hi*mid, hi*hi; the three dropped ones are below 2^-26 of the product.
+// The partial product is outermost, so that an accumulator is re-used NG instructions later.  PIX_FIRST: the pixels are the first MFMA operand
+// (D[pixel][cout]), else the weights (D[cout][pixel]).  Bit-equality between the fused kernels and the launches they replace rests on every
+// split kernel issuing this order per accumulator: conv2d_tiled.h (DMVS_SPLIT_PRODUCT) and conv1_pair.hip (conv_group, which interleaves its
+// operand reads with the six instructions) spell it out by hand.
+template <int NG, bool PIX_FIRST>
+__device__ __forceinline__ void dmvs_split_step(const bf16x8* ph, const bf16x8* pm, const bf16x8* pl, const bf16x8& wh, const bf16x8& wm, const bf16x8& wl, f32x4_bf* acc) {
+    auto mf = [&](const bf16x8* p, const bf16x8& w) __attribute__((always_inline)) {
+#pragma unroll
+        for (int g = 0; g < NG; ++g) acc[g] = PIX_FIRST ? dmvs_mfma_bf16(p[g], w, acc[g]) : dmvs_mfma_bf16(w, p[g], acc[g]);
+    };
+    mf(pl, wh);
+    mf(ph, wl);
+    mf(pm, wm);
+    mf(pm, wh);
+    mf(ph, wm);
+    mf(ph, wh);
+}
+
+// Four fp32 values as bf16 triples into k-slots 0-3 or 4-7 of a [plane hi / mid / lo][position][8 channels] image: one 8-byte store per plane.
+// dst = the half entry of the hi plane, plane_u32x2 = a plane's size in 8-byte units.
+typedef uint32_t dmvs_u32x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t dmvs_u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void dmvs_store_split4(const float (&v4)[4], dmvs_u32x2* dst, int plane_u32x2) {
+    const float v[8] = {v4[0], v4[1], v4[2], v4[3], 0.0f, 0.0f, 0.0f, 0.0f};
+    bf16x8 h8, m8, l8;
+    dmvs_split3_bf16x8(v, h8, m8, l8);
+    const dmvs_u32x4 hh = __builtin_bit_cast(dmvs_u32x4, h8), mm = __builtin_bit_cast(dmvs_u32x4, m8), ll = __builtin_bit_cast(dmvs_u32x4, l8);
+    dst[0] = dmvs_u32x2{hh[0], hh[1]};
+    dst[plane_u32x2] = dmvs_u32x2{mm[0], mm[1]};
+    dst[2 * plane_u32x2] = dmvs_u32x2{ll[0], ll[1]};
+}

@@ -38,27 +38,46 @@
     } while (0)
 #endif
 
+// The LDS destination of __builtin_amdgcn_global_load_lds (LDS-DMA), and the all-zero 16-byte source of the pieces that stage padding
+// (an LDS-DMA lane cannot write a literal).
+#define DMVS_LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
+__device__ __attribute__((aligned(16))) const float dmvs_zero16[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+
+// Opaque redefinition of a lane coordinate at the top of every step of a persistent workgroup's tile / row loop: without it hipcc hoists
+// every lane-dependent address of the step out of the loop, keeps them all live and spills (conv2d_tiled.h: 112 instead of 63 VGPRs).
+#ifdef DMVS_HOST_EMULATION
+#define DMVS_OPAQUE(v) ((void)0)
+#else
+#define DMVS_OPAQUE(v) asm volatile("" : "+v"(v))
+#endif
+
 static inline int dmvs_launch_status() {
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : (int)e;
 }
 
-// Workgroups of `kernel` (256 threads, static LDS only) the whole chip holds at once: the grid of a resident, tile-walking
+// Workgroups of `kernel` (`block_threads` threads, static LDS only) the whole chip holds at once: the grid of a resident, tile-walking
 // launch.  The occupancy query over-reports by one workgroup per CU for SGPR-heavy kernels at 7-8 per CU
 // (MI355X_MICROARCH.md, residency) -- and a surplus workgroup would start only when a resident one has walked ALL its tiles
 // (a tail as long as the launch) -- so the count is capped at 6 per CU, below that band.
 #ifdef DMVS_HOST_EMULATION
-static inline int dmvs_resident_workgroups(const void*) { return 2; }       // (so that the CPU tests walk several tiles per workgroup)
+static inline int dmvs_resident_workgroups(const void*, int = DMVS_BLOCK) { return 2; }       // (so that the CPU tests walk several tiles per workgroup)
 #else
-static inline int dmvs_resident_workgroups(const void* kernel) {
+static inline int dmvs_resident_workgroups(const void* kernel, int block_threads = DMVS_BLOCK) {
     int dev = 0, per_cu = 0;
     hipDeviceProp_t prop;
     if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 256;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, DMVS_BLOCK, 0) != hipSuccess || per_cu < 1) per_cu = 1;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block_threads, 0) != hipSuccess || per_cu < 1) per_cu = 1;
     if (per_cu > 6) per_cu = 6;
     return per_cu * prop.multiProcessorCount;
 }
 #endif
+// The grid of a persistent launch over `nunits` work units: the resident workgroups, or tune & 0xffff where a caller forces it (tests:
+// results do not depend on the grid).
+static inline unsigned dmvs_persistent_grid(int tune, int resident, long nunits) {
+    const long grid = (tune & 0xffff) ? (tune & 0xffff) : resident;
+    return (unsigned)(grid < nunits ? grid : nunits);
+}
 
 static inline unsigned dmvs_ceil_div(long a, long b) { return (unsigned)((a + b - 1) / b); }
 __device__ __forceinline__ unsigned dmvs_ceil_div_dev(long a, long b) { return (unsigned)((a + b - 1) / b); }

@@ -39,37 +39,26 @@
 // at W % 32 == 0.
 
 #include "dmvs_common.h"
-#include "dmvs_bf16.h"
+#include "dmvs_ring.h"
 #include "dmvs_lds_poison.h"
 
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4s __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2s __attribute__((ext_vector_type(2)));
 
 constexpr int PB = 256;                     // threads per workgroup
 constexpr int US = 32, UR = 64;             // a unit's output columns / rows
 constexpr int NP = US + 2;                  // ring positions per row: columns X0 - 1 .. X0 + 32
-constexpr int SLOTS = 4, NCH = 8;           // ring row slots, chunks of 8 intra channels
-constexpr int PLQ = SLOTS * NCH * NP;       // 16-byte entries of one bf16 plane: [slot][chunk][position]
-constexpr int RINGQ = 3 * PLQ;              // the ring: 52,224 bytes
+constexpr int NCH = 8;                      // chunks of 8 intra channels
+typedef dmvs_ring<NCH, NP> Ring;            // 52,224 bytes
+constexpr int PLQ = Ring::PLQ, RINGQ = Ring::RINGQ;
 constexpr int SW = US + 8;                  // a staged c2 row: the 16-byte aligned cover of columns X0 - 1 .. X0 + 32 = columns X0 - 4 .. X0 + 35
 constexpr int C2PIECE = 2 * 32 * SW / 4;    // [2 rows][32 channels][40]: 640 16-byte pieces
 constexpr int CW = US / 2 + 8;              // a staged c3 row: c3 columns X0 / 2 - 4 .. X0 / 2 + 19 (needed: X0 / 2 - 1 .. X0 / 2 + 16)
 constexpr int C3PIECE = 64 * CW / 4;        // [64 channels][24]: 384 pieces per row slot
 constexpr int LDSF = RINGQ * 4 + C2PIECE * 4 + 2 * C3PIECE * 4;
 constexpr int NSTEP = NCH * 3;              // (chunk, tap group) steps of an output row
-
-__device__ __attribute__((aligned(16))) const float fpn_tail_zero16[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-#define DMVS_LDS_P(p) ((__attribute__((address_space(3))) void*)(p))
-// Opaque redefinition of a lane coordinate at the top of every step (conv1_pair.hip): keeps hipcc from hoisting every lane-dependent address of the
-// step out of the step loop
-#ifdef DMVS_HOST_EMULATION
-#define DMVS_OPAQUE(v) ((void)0)
-#else
-#define DMVS_OPAQUE(v) asm volatile("" : "+v"(v))
-#endif
 
 __global__ void __launch_bounds__(PB) __attribute__((amdgpu_waves_per_eu(2, 2)))      // two workgroups per CU (LDS): 2 waves per SIMD
 featurenet_fpn_tail_kernel(const float* __restrict__ c2, const float* __restrict__ c3, const float* __restrict__ w1, const float* __restrict__ b1,
@@ -96,12 +85,9 @@ featurenet_fpn_tail_kernel(const float* __restrict__ c2, const float* __restrict
     auto wload = [&](int sp) -> u32x4s {      // uniform slab base + 32-bit lane offset: one address register for all 72 loads of a row
         return *reinterpret_cast<const u32x4s*>(reinterpret_cast<const char*>(ws2 + sp * 128) + lwb);
     };
-    int taps = 0;       // (ky | kx << 2) of tap group g in bits 4g .. 4g + 3
+    int taps = 0;       // (ky | kx << 2) of tap group g in bits 4g .. 4g + 3: dmvs_ring::operand
 #pragma unroll
-    for (int g = 0; g < 3; ++g) {
-        const int t = min(4 * g + kq, 8);      // (a tap slot beyond the kernel meets zero weights)
-        taps |= ((t / 3) | ((t % 3) << 2)) << (4 * g);
-    }
+    for (int g = 0; g < 3; ++g) taps |= dmvs_tap_slot<3, 3, 2>(g, kq) << (4 * g);
     u32x4s* const ring = reinterpret_cast<u32x4s*>(lds);
     float* const st2 = lds + RINGQ * 4;
     float* const st3 = st2 + C2PIECE * 4;
@@ -109,11 +95,8 @@ featurenet_fpn_tail_kernel(const float* __restrict__ c2, const float* __restrict
     int lm = m, ltid = tid;      // (redefined opaquely per step)
 
     for (int unit = blockIdx.x; unit < nunits; unit += gridDim.x) {
-        const int sx = unit % nsx;
-        const int uq = unit / nsx;
-        const int sy = uq % nsy, n = uq / nsy;
-        const int X0 = US * sx, Y0 = UR * sy;
-        const int Yend = min(Y0 + UR, H) - 1;
+        const dmvs_unit u(unit, nsx, nsy, US, UR, H);
+        const int n = u.n, X0 = u.X0, Y0 = u.Y0, Yend = u.Yend;
         const int Q = (Yend - Y0 + 1) >> 1;      // output row pairs (H is even): intra pairs 0 .. Q, steps 0 .. Q + 1
         const float* const c2b = c2 + (long)n * 32 * iplane;
         const float* const c3b = c3 + (long)n * 64 * iplane3;
@@ -130,25 +113,17 @@ featurenet_fpn_tail_kernel(const float* __restrict__ c2, const float* __restrict
                     const int ch = e / (CW / 4), pc = e - ch * (CW / 4);
                     const int col = (X0 >> 1) - 4 + 4 * pc;
                     const bool ok = row3 >= 0 && row3 < H2 && col >= 0 && col < W2;
-                    const float* srcp = ok ? c3b + (ch * iplane3 + row3 * W2 + col) : fpn_tail_zero16;
+                    const float* srcp = ok ? c3b + (ch * iplane3 + row3 * W2 + col) : dmvs_zero16;
                     float* dstp = st3 + (((row3 + 2) & 1) * C3PIECE + k * PB + wave * 64) * 4;
-                    __builtin_amdgcn_global_load_lds(srcp, DMVS_LDS_P(dstp), 16, 0, 0);
+                    __builtin_amdgcn_global_load_lds(srcp, DMVS_LDS_PTR(dstp), 16, 0, 0);
                 }
             }
         };
         auto stage = [&](int p, bool with_above, int lt) {
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
-                if (k * PB + wave * 64 < C2PIECE) {      // (wave-uniform: 640 pieces = 10 waves' worth)
-                    const int e = k * PB + lt;
-                    const int li = e / (C2PIECE / 2), rem = e - li * (C2PIECE / 2);
-                    const int ch = rem / (SW / 4), pc = rem - ch * (SW / 4);
-                    const int row = Y0 - 1 + 2 * p + li, col = X0 - 4 + 4 * pc;
-                    const bool ok = row >= 0 && row < H && col >= 0 && col < W;
-                    const float* srcp = ok ? c2b + (ch * iplane + row * W + col) : fpn_tail_zero16;
-                    float* dstp = st2 + (k * PB + wave * 64) * 4;
-                    __builtin_amdgcn_global_load_lds(srcp, DMVS_LDS_P(dstp), 16, 0, 0);
-                }
+                if (k * PB + wave * 64 < C2PIECE)      // (wave-uniform: 640 pieces = 10 waves' worth)
+                    dmvs_stage_piece<2, 32, SW>(c2b, iplane, H, W, Y0 - 1 + 2 * p, X0 - 4, true, k * PB + lt, st2 + (k * PB + wave * 64) * 4);
             }
             stage_c3((Y0 >> 1) + p, lt);
             if (with_above) stage_c3((Y0 >> 1) + p - 1, lt);
@@ -165,14 +140,9 @@ featurenet_fpn_tail_kernel(const float* __restrict__ c2, const float* __restrict
             const int orow = Y0 + 2 * (j - 2) + rr;
             f32x4 oacc[2] = {{0.0f, 0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f, 0.0f}};
             if (do_out) {
-                auto qp_of = [&](int s) {
-                    const int c = s / 3, g = s - c * 3;
-                    const int tg = taps >> (4 * g);
-                    const int slot = (orow + 3 + (tg & 3)) & 3;              // source row orow - 1 + ky
-                    return (slot * NCH + c) * NP + lm + ((tg >> 2) & 3);
-                };
+                auto qp_of = [&](int s) { return Ring::operand(s, taps, orow, lm); };
                 u32x4s wq[3][3];         // [register set][plane]: the weights of steps s, s + 1, s + 2
-                bf16x8 pq[2][2][3];      // [register set][group][plane]: the pixel operands of steps s, s + 1
+                bf16x8 pq[2][3][2];      // [register set][plane][group]: the pixel operands of steps s, s + 1
 #pragma unroll
                 for (int s0 = 0; s0 < 2; ++s0)
 #pragma unroll
@@ -182,7 +152,7 @@ featurenet_fpn_tail_kernel(const float* __restrict__ c2, const float* __restrict
 #pragma unroll
                     for (int grp = 0; grp < 2; ++grp)
 #pragma unroll
-                        for (int pl = 0; pl < 3; ++pl) pq[0][grp][pl] = __builtin_bit_cast(bf16x8, ring[pl * PLQ + qp + 16 * grp]);
+                        for (int pl = 0; pl < 3; ++pl) pq[0][pl][grp] = __builtin_bit_cast(bf16x8, ring[pl * PLQ + qp + 16 * grp]);
                 }
 #pragma unroll
                 for (int s = 0; s < NSTEP; ++s) {
@@ -197,24 +167,12 @@ featurenet_fpn_tail_kernel(const float* __restrict__ c2, const float* __restrict
 #pragma unroll
                         for (int grp = 0; grp < 2; ++grp)
 #pragma unroll
-                            for (int pl = 0; pl < 3; ++pl) pq[pb ^ 1][grp][pl] = __builtin_bit_cast(bf16x8, ring[pl * PLQ + qn + 16 * grp]);
+                            for (int pl = 0; pl < 3; ++pl) pq[pb ^ 1][pl][grp] = __builtin_bit_cast(bf16x8, ring[pl * PLQ + qn + 16 * grp]);
                     }
                     __builtin_amdgcn_sched_barrier(0);
-                    const bf16x8 wh = __builtin_bit_cast(bf16x8, wq[wb][0]), wm = __builtin_bit_cast(bf16x8, wq[wb][1]),
-                                 wlo = __builtin_bit_cast(bf16x8, wq[wb][2]);
-                    // the six partial products, smallest first; the two groups' MFMAs of one product are independent
-#pragma unroll
-                    for (int grp = 0; grp < 2; ++grp) oacc[grp] = dmvs_mfma_bf16(wh, pq[pb][grp][2], oacc[grp]);
-#pragma unroll
-                    for (int grp = 0; grp < 2; ++grp) oacc[grp] = dmvs_mfma_bf16(wlo, pq[pb][grp][0], oacc[grp]);
-#pragma unroll
-                    for (int grp = 0; grp < 2; ++grp) oacc[grp] = dmvs_mfma_bf16(wm, pq[pb][grp][1], oacc[grp]);
-#pragma unroll
-                    for (int grp = 0; grp < 2; ++grp) oacc[grp] = dmvs_mfma_bf16(wh, pq[pb][grp][1], oacc[grp]);
-#pragma unroll
-                    for (int grp = 0; grp < 2; ++grp) oacc[grp] = dmvs_mfma_bf16(wm, pq[pb][grp][0], oacc[grp]);
-#pragma unroll
-                    for (int grp = 0; grp < 2; ++grp) oacc[grp] = dmvs_mfma_bf16(wh, pq[pb][grp][0], oacc[grp]);
+                    // (the two groups' MFMAs of one product are independent)
+                    dmvs_split_step<2, false>(pq[pb][0], pq[pb][1], pq[pb][2], __builtin_bit_cast(bf16x8, wq[wb][0]), __builtin_bit_cast(bf16x8, wq[wb][1]),
+                                              __builtin_bit_cast(bf16x8, wq[wb][2]), oacc);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -258,22 +216,8 @@ featurenet_fpn_tail_kernel(const float* __restrict__ c2, const float* __restrict
                     const int row = Y0 - 1 + 2 * j + li;
                     const int pp = grp * 16 + m;
                     if (pp < NP) {
-                        float v[8];
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            v[r] = iv[it][r];
-                            v[4 + r] = 0.0f;
-                        }
-                        bf16x8 h8, m8, l8;
-                        dmvs_split3_bf16x8(v, h8, m8, l8);
                         // channels 16 wave + 4 kq .. + 3 = chunk 2 wave + (kq >> 1), k-slots 4 (kq & 1) .. + 3: 8 bytes per plane
-                        u32x2s* const d = reinterpret_cast<u32x2s*>(ring + ((((row + 4) & 3) * NCH + 2 * wave + (kq >> 1)) * NP + pp)) + (kq & 1);
-                        auto pack4 = [](const bf16x8& b) {
-                            return u32x2s{(uint32_t)(uint16_t)b[0] | ((uint32_t)(uint16_t)b[1] << 16), (uint32_t)(uint16_t)b[2] | ((uint32_t)(uint16_t)b[3] << 16)};
-                        };
-                        d[0] = pack4(h8);
-                        d[PLQ * 2] = pack4(m8);
-                        d[2 * PLQ * 2] = pack4(l8);
+                        dmvs_store_split4(iv[it], reinterpret_cast<dmvs_u32x2*>(ring + Ring::index(row, 2 * wave + (kq >> 1), pp)) + (kq & 1), PLQ * 2);
                     }
                 }
             }
@@ -281,19 +225,6 @@ featurenet_fpn_tail_kernel(const float* __restrict__ c2, const float* __restrict
         }
     }
 }
-
-#ifdef DMVS_HOST_EMULATION
-int fpn_tail_resident() { return 2; }
-#else
-int fpn_tail_resident() {
-    int dev = 0, per_cu = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 512;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(featurenet_fpn_tail_kernel), PB, 0) != hipSuccess || per_cu < 1)
-        per_cu = 1;
-    return per_cu * prop.multiProcessorCount;
-}
-#endif
 
 }  // namespace
 
@@ -308,10 +239,8 @@ extern "C" int dmvs_featurenet_fpn_tail_f32(const float* c2, const float* c3, co
     const long nunits = (long)nsx * nsy * N;
     if (nunits >= (1L << 31)) return DMVS_EINVAL;
     // persistent workgroups: as many as are resident at once; tune & 0xffff forces the grid (tests: results do not depend on it)
-    static const int resident = fpn_tail_resident();
-    long grid = (tune & 0xffff) ? (tune & 0xffff) : resident;
-    if (grid > nunits) grid = nunits;
-    hipLaunchKernelGGL(featurenet_fpn_tail_kernel, dim3((unsigned)grid), dim3(PB), 0, (hipStream_t)stream, c2, c3, w_inner, b_inner,
+    static const int resident = dmvs_resident_workgroups(reinterpret_cast<const void*>(featurenet_fpn_tail_kernel), PB);
+    hipLaunchKernelGGL(featurenet_fpn_tail_kernel, dim3(dmvs_persistent_grid(tune, resident, nunits)), dim3(PB), 0, (hipStream_t)stream, c2, c3, w_inner, b_inner,
                        reinterpret_cast<const u32x4s*>(wsplit_out), y, N, H, W, nsx, nsy);
     return dmvs_launch_status();
 }

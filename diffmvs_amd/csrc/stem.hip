@@ -25,13 +25,12 @@
 // so a split would cost more VALU work than the matrix time it saves.  DMVS_TUNE_STEM_EXACT: the exact-fp32 conv0.1.
 
 #include "dmvs_common.h"
-#include "dmvs_bf16.h"
+#include "dmvs_ring.h"
 #include "dmvs_lds_poison.h"
 
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-#define DMVS_LDS_S(p) ((__attribute__((address_space(3))) void*)(p))
 
 constexpr int TS = 16;                 // output tile
 constexpr int MW = TS + 2, MP = MW * MW;          // intermediate tile 18 x 18 = 324
@@ -45,8 +44,6 @@ constexpr int K0 = 36, K0S = K0 / 4;               // conv0.0: (ci, input row j,
 // instructions.  Needs rows of 16-byte multiples on a 16-byte aligned tensor; a piece lies wholly inside or outside the image.
 constexpr int IWL16 = 24, SLACK16 = 2;
 constexpr int W1S = 208;                           // conv0.1 paired weight slab [j 4][kx 3][16 rows] per input channel, padded (192 -> 16 mod 32)
-
-__device__ __attribute__((aligned(16))) const float stem_zero16[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 
 template <bool V16, bool SPLIT>
 __global__ void __launch_bounds__(DMVS_BLOCK)
@@ -86,22 +83,9 @@ featurenet_stem_kernel(const float* __restrict__ x, const float* __restrict__ w0
         s_w1[e] = (jt < 12 && ky >= 0 && ky <= 2) ? w1[(ci * 9 + ky * 3 + kx) * 8 + (row & 7)] : 0.0f;
     }
     }
-    // (SPLIT) this lane's paired conv0.1 weights as bf16 triples, for the life of the workgroup: matrix column m = (output row of the pair m >> 3,
-    // cout m & 7), k-slots = the 8 input channels of slot s = 4g + kq of the 12 (input row j, kx) slots: rows 0-7 take tap row ky = j, rows 8-15 ky = j - 1
+    // (SPLIT) this lane's paired conv0.1 weights as bf16 triples, for the life of the workgroup (matrix COLUMN m here: the pixels are the A operand)
     [[maybe_unused]] bf16x8 w1h[3], w1m[3], w1l[3];
-    if constexpr (SPLIT) {
-        const int mrow = threadIdx.x & 15;
-#pragma unroll
-        for (int g = 0; g < 3; ++g) {
-            const int sl = 4 * g + ((threadIdx.x & 63) >> 4);
-            const int j = sl / 3, kx = sl - j * 3;
-            const int ky = mrow < 8 ? j : j - 1;
-            float wv[8];
-#pragma unroll
-            for (int ci = 0; ci < 8; ++ci) wv[ci] = (ky >= 0 && ky <= 2) ? w1[(ci * 9 + ky * 3 + kx) * 8 + (mrow & 7)] : 0.0f;
-            dmvs_split3_bf16x8(wv, w1h[g], w1m[g], w1l[g]);
-        }
-    }
+    if constexpr (SPLIT) dmvs_conv01_paired_weights(w1, threadIdx.x & 15, (threadIdx.x & 63) >> 4, w1h, w1m, w1l);
 
     // Input halo staging (3 x 20 x 20, zero padded): 4-byte LDS-DMA, 64 consecutive words per wave.  Which (channel,
     // row, column) a lane's pieces are is tile-independent: decoded once; per tile the border test is one packed compare
@@ -140,13 +124,13 @@ featurenet_stem_kernel(const float* __restrict__ x, const float* __restrict__ w0
             if (e_rc[i] >= 0) {
                 const unsigned rc = (unsigned)e_rc[i];
                 const bool ok = (((rc | kGuard) - lo) & (him1 - rc) & kGuard) == kGuard;
-                const float* srcp = ok ? origin + e_off[i] : stem_zero16;
+                const float* srcp = ok ? origin + e_off[i] : dmvs_zero16;
                 if constexpr (V16) {
                     float* dstp = buf + (i * DMVS_BLOCK + wave * 64) * 4;
-                    __builtin_amdgcn_global_load_lds(srcp, DMVS_LDS_S(dstp), 16, 0, 0);
+                    __builtin_amdgcn_global_load_lds(srcp, DMVS_LDS_PTR(dstp), 16, 0, 0);
                 } else {
                     float* dstp = buf + i * DMVS_BLOCK + wave * 64;
-                    __builtin_amdgcn_global_load_lds(srcp, DMVS_LDS_S(dstp), 4, 0, 0);
+                    __builtin_amdgcn_global_load_lds(srcp, DMVS_LDS_PTR(dstp), 4, 0, 0);
                 }
             }
         }
@@ -231,21 +215,10 @@ featurenet_stem_kernel(const float* __restrict__ x, const float* __restrict__ w0
             if (gidx * 16 + m < NSLOT) {
                 if constexpr (SPLIT) {
                     // the lane's 4 channels 4 * (kq & 1) + r of position (py, px) as bf16 triples: 8 bytes per plane
-                    float v[8];
+                    float v[4];
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        v[r] = inside ? fmaxf(fmaf(acc[r], sc0[r], sh0[r]), 0.0f) : 0.0f;
-                        v[4 + r] = 0.0f;
-                    }
-                    bf16x8 h8, m8, l8;
-                    dmvs_split3_bf16x8(v, h8, m8, l8);
-                    typedef uint32_t u32x2s __attribute__((ext_vector_type(2)));
-                    typedef uint32_t u32x4s __attribute__((ext_vector_type(4)));
-                    u32x2s* const q = reinterpret_cast<u32x2s*>(s_mid) + (py * MW + px) * 2 + (kq & 1);
-                    const u32x4s hh = __builtin_bit_cast(u32x4s, h8), mm = __builtin_bit_cast(u32x4s, m8), ll = __builtin_bit_cast(u32x4s, l8);
-                    q[0] = u32x2s{hh[0], hh[1]};
-                    q[MP * 2] = u32x2s{mm[0], mm[1]};
-                    q[2 * MP * 2] = u32x2s{ll[0], ll[1]};
+                    for (int r = 0; r < 4; ++r) v[r] = inside ? fmaxf(fmaf(acc[r], sc0[r], sh0[r]), 0.0f) : 0.0f;
+                    dmvs_store_split4(v, reinterpret_cast<dmvs_u32x2*>(s_mid) + (py * MW + px) * 2 + (kq & 1), MP * 2);
                 } else {
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
@@ -277,19 +250,7 @@ featurenet_stem_kernel(const float* __restrict__ x, const float* __restrict__ w0
                     pm[pr] = __builtin_bit_cast(bf16x8, q_mid[qp]);
                     pl[pr] = __builtin_bit_cast(bf16x8, q_lo[qp]);
                 }
-                // the partial product outermost (the two row pairs are independent accumulators), smallest products first
-#pragma unroll
-                for (int pr = 0; pr < 2; ++pr) acc[pr] = dmvs_mfma_bf16(pl[pr], w1h[g], acc[pr]);
-#pragma unroll
-                for (int pr = 0; pr < 2; ++pr) acc[pr] = dmvs_mfma_bf16(ph[pr], w1l[g], acc[pr]);
-#pragma unroll
-                for (int pr = 0; pr < 2; ++pr) acc[pr] = dmvs_mfma_bf16(pm[pr], w1m[g], acc[pr]);
-#pragma unroll
-                for (int pr = 0; pr < 2; ++pr) acc[pr] = dmvs_mfma_bf16(pm[pr], w1h[g], acc[pr]);
-#pragma unroll
-                for (int pr = 0; pr < 2; ++pr) acc[pr] = dmvs_mfma_bf16(ph[pr], w1m[g], acc[pr]);
-#pragma unroll
-                for (int pr = 0; pr < 2; ++pr) acc[pr] = dmvs_mfma_bf16(ph[pr], w1h[g], acc[pr]);
+                dmvs_split_step<2, true>(ph, pm, pl, w1h[g], w1m[g], w1l[g], acc);      // (the two row pairs are independent accumulators)
             }
         } else {
 #pragma unroll

@@ -21,7 +21,7 @@
 // Halo recompute: conv0.1 (67 x 68)/(64 x 64), conv0.0 (69 x 70)/(64 x 64) -- stem.hip's 18 x 18 tile costs 1.27 for conv0.0.
 
 #include "dmvs_common.h"
-#include "dmvs_bf16.h"
+#include "dmvs_ring.h"
 #include "dmvs_lds_poison.h"
 
 #include <type_traits>
@@ -29,9 +29,7 @@
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2s __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4s __attribute__((ext_vector_type(4)));
-#define DMVS_LDS_S(p) ((__attribute__((address_space(3))) void*)(p))
 
 constexpr int UC = 32, UR = 32;                     // a unit's output columns / rows (half resolution)
 constexpr int INW = 72;                             // input ring row: the 16-byte aligned cover of columns 2*ox0 - 4 .. + 67
@@ -44,8 +42,6 @@ constexpr int MPL = 8 * MW, CPL = 8 * CW;           // one bf16 plane [8 rows][p
 constexpr int MIDF = 3 * MPL * 4, C0F = 3 * CPL * 4;
 constexpr int K0S = 9;                              // conv0.0: 36 k-slots = 9 MFMA steps
 constexpr int K2S = 7;                              // conv1.0: 28 tap slots x 8 channels = 7 bf16 MFMA steps
-
-__device__ __attribute__((aligned(16))) const float stem3_zero16[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 
 __global__ void __launch_bounds__(DMVS_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))      // two workgroups per CU (LDS): at most 256 registers
 featurenet_stem3_kernel(const float* __restrict__ x, const float* __restrict__ w0, const float* __restrict__ scale0, const float* __restrict__ shift0,
@@ -88,33 +84,23 @@ featurenet_stem3_kernel(const float* __restrict__ x, const float* __restrict__ w
         sc1[r] = scale1 ? scale1[co] : 1.0f;
         sh1[r] = shift1 ? shift1[co] : 0.0f;
     }
-    // conv0.1: the lane's paired weights as bf16 triples (stem.hip): matrix row m = (c0 row of the pair m >> 3, cout m & 7), k-slots = the 8 input
-    // channels of slot sl = 4g + kq of the 12 (mid row j, kx) slots
+    // conv0.1: the lane's paired weights as bf16 triples (matrix ROW m: the weights are the A operand), and its (mid row j, kx) slot of every step
     bf16x8 w1h[3], w1m[3], w1l[3];
     int off1[3];        // j | kx << 4
 #pragma unroll
-    for (int g = 0; g < 3; ++g) {
-        const int sl = 4 * g + kq;
-        const int j = sl / 3, kx = sl - j * 3;
-        const int ky = m < 8 ? j : j - 1;
-        float wv[8];
-#pragma unroll
-        for (int ci = 0; ci < 8; ++ci) wv[ci] = (ky >= 0 && ky <= 2) ? w1[(ci * 9 + ky * 3 + kx) * 8 + (m & 7)] : 0.0f;
-        dmvs_split3_bf16x8(wv, w1h[g], w1m[g], w1l[g]);
-        off1[g] = j | (kx << 4);
-    }
+    for (int g = 0; g < 3; ++g) off1[g] = dmvs_tap_slot<4, 3>(g, kq);
+    dmvs_conv01_paired_weights(w1, m, kq, w1h, w1m, w1l);
     // conv1.0: B = w2[k = (tap slot sl = 4s + kq, channel j)][cout m] as bf16 triples; slots 25-27 carry zero weights and read tap 24's operand
     bf16x8 w2h[K2S], w2m[K2S], w2l[K2S];
     int off2[K2S];      // ky | kx << 4
 #pragma unroll
     for (int s = 0; s < K2S; ++s) {
         const int sl = 4 * s + kq;
-        const int tp = min(sl, 24);
         float wv[8];
 #pragma unroll
         for (int ci = 0; ci < 8; ++ci) wv[ci] = sl < 25 ? w2[(ci * 25 + sl) * 16 + m] : 0.0f;
         dmvs_split3_bf16x8(wv, w2h[s], w2m[s], w2l[s]);
-        off2[s] = (tp / 5) | ((tp % 5) << 4);
+        off2[s] = dmvs_tap_slot<5, 5>(s, kq);
     }
     const float sc2 = scale2 ? scale2[m] : 1.0f, sh2 = shift2 ? shift2[m] : 0.0f;
     const bool vec = (Wo & 3) == 0 && ((uintptr_t)y & 15) == 0;
@@ -124,21 +110,19 @@ featurenet_stem3_kernel(const float* __restrict__ x, const float* __restrict__ w
     const int p_i = tid / (NPIECE / 4), p_rem = tid - p_i * (NPIECE / 4);
     const int p_ci = p_rem / (INW / 4), p_c = (p_rem - p_ci * (INW / 4)) * 4;
     auto stage = [&](int unit, int kg, int slot) {
-        const int sx = unit % nsx;
-        const int uq = unit / nsx;
-        const int sy = uq % nsy, n = uq / nsy;
-        const int row = 2 * UR * sy - 5 + 4 * kg + p_i, col = 2 * UC * sx - 4 + p_c;
+        const dmvs_unit u(unit, nsx, nsy, UC, UR, Ho);
+        const int row = 2 * u.Y0 - 5 + 4 * kg + p_i, col = 2 * u.X0 - 4 + p_c;
         if (tid < NPIECE) {
             const bool ok = row >= 0 && row < H && col >= 0 && col < W;
-            const float* srcp = ok ? x + ((long)n * 3 + p_ci) * plane + (long)row * W + col : stem3_zero16;
+            const float* srcp = ok ? x + ((long)u.n * 3 + p_ci) * plane + (long)row * W + col : dmvs_zero16;
             float* dstp = s_in + slot * INGRP + wave * 256;
-            __builtin_amdgcn_global_load_lds(srcp, DMVS_LDS_S(dstp), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds(srcp, DMVS_LDS_PTR(dstp), 16, 0, 0);
         }
     };
 
     auto steps_of = [&](int unit) {      // two output rows per step, two warm-up steps
-        const int sy = (unit / nsx) % nsy;
-        return ((min(UR, Ho - UR * sy) + 1) >> 1) + 2;
+        const dmvs_unit u(unit, nsx, nsy, UC, UR, Ho);
+        return ((u.Yend - u.Y0 + 2) >> 1) + 2;
     };
     // the staging cursor runs TWO groups ahead of the step, across unit boundaries: a group is issued right behind the DMA-publishing barrier
     // of step k - 2 and waited for at that of step k - 1, so it has a whole step to land
@@ -160,10 +144,8 @@ featurenet_stem3_kernel(const float* __restrict__ x, const float* __restrict__ w
     stage_next();
     DMVS_DMA_BARRIER();
     for (; unit < nunits; unit += gridDim.x) {
-        const int sx = unit % nsx;
-        const int uq = unit / nsx;
-        const int sy = uq % nsy, n = uq / nsy;
-        const int X0 = 2 * UC * sx, Y0 = 2 * UR * sy, ox0 = UC * sx, oy0 = UR * sy;
+        const dmvs_unit u(unit, nsx, nsy, UC, UR, Ho);      // in output (half-resolution) columns and rows
+        const int n = u.n, ox0 = u.X0, oy0 = u.Y0, X0 = 2 * ox0, Y0 = 2 * oy0;
         const int nsteps = steps_of(unit);
         for (int k = 0; k < nsteps; ++k, pslot = islot, islot = islot == INSLOTS - 1 ? 0 : islot + 1) {
             // ---- conv0.0 -> mid rows 4k .. 4k+3: slots (row pair q, position) row-major over 2 x 69, 16 per MFMA group; step 0 needs pair 1 only.
@@ -201,19 +183,10 @@ featurenet_stem3_kernel(const float* __restrict__ x, const float* __restrict__ w
                         const int gy = Y0 - 6 + ml, gx = X0 - 3 + pm[i];
                         const bool inside = gy >= 0 && gy < H && gx >= 0 && gx < W;
                         if (sbeg + (g0 + 4 * i) * 16 + m < 2 * MW) {
-                            float v[8];
+                            float v[4];
 #pragma unroll
-                            for (int r = 0; r < 4; ++r) {
-                                v[r] = inside ? fmaxf(fmaf(acc[i][r], sc0[r], sh0[r]), 0.0f) : 0.0f;
-                                v[4 + r] = 0.0f;
-                            }
-                            bf16x8 h8, m8, l8;
-                            dmvs_split3_bf16x8(v, h8, m8, l8);
-                            u32x2s* const d = reinterpret_cast<u32x2s*>(s_mid) + ((ml & 7) * MW + pm[i]) * 2 + (kq & 1);
-                            const u32x4s hh = __builtin_bit_cast(u32x4s, h8), mm = __builtin_bit_cast(u32x4s, m8), ll = __builtin_bit_cast(u32x4s, l8);
-                            d[0] = u32x2s{hh[0], hh[1]};
-                            d[MPL * 2] = u32x2s{mm[0], mm[1]};
-                            d[2 * MPL * 2] = u32x2s{ll[0], ll[1]};
+                            for (int r = 0; r < 4; ++r) v[r] = inside ? fmaxf(fmaf(acc[i][r], sc0[r], sh0[r]), 0.0f) : 0.0f;
+                            dmvs_store_split4(v, reinterpret_cast<dmvs_u32x2*>(s_mid) + ((ml & 7) * MW + pm[i]) * 2 + (kq & 1), MPL * 2);
                         }
                     }
                 };
@@ -243,32 +216,16 @@ featurenet_stem3_kernel(const float* __restrict__ x, const float* __restrict__ w
                     }
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                    for (int g3 = 0; g3 < 3; ++g3) {
-                        acc = dmvs_mfma_bf16(w1h[g3], pl[g3], acc);
-                        acc = dmvs_mfma_bf16(w1l[g3], ph[g3], acc);
-                        acc = dmvs_mfma_bf16(w1m[g3], pmid[g3], acc);
-                        acc = dmvs_mfma_bf16(w1h[g3], pmid[g3], acc);
-                        acc = dmvs_mfma_bf16(w1m[g3], ph[g3], acc);
-                        acc = dmvs_mfma_bf16(w1h[g3], ph[g3], acc);
-                    }
+                    for (int g3 = 0; g3 < 3; ++g3) dmvs_split_step<1, false>(&ph[g3], &pmid[g3], &pl[g3], w1h[g3], w1m[g3], w1l[g3], &acc);
                     // D[row = 4*kq + r][col = m]: rows 0-7 = the 8 channels of c0 pixel (4k + 2 pr, pc), rows 8-15 = those of the row below
                     const int cl = 4 * k + 2 * pr + (kq >> 1);
                     const int gy = Y0 - 7 + cl, gx = X0 - 2 + pc;
                     const bool inside = gy >= 0 && gy < H && gx >= 0 && gx < W;
                     if (g * 16 + m < 2 * CW) {
-                        float v[8];
+                        float v[4];
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            v[r] = inside ? fmaxf(fmaf(acc[r], sc1[r], sh1[r]), 0.0f) : 0.0f;
-                            v[4 + r] = 0.0f;
-                        }
-                        bf16x8 h8, m8, l8;
-                        dmvs_split3_bf16x8(v, h8, m8, l8);
-                        u32x2s* const d = reinterpret_cast<u32x2s*>(s_c0) + ((cl & 7) * CW + pc) * 2 + (kq & 1);
-                        const u32x4s hh = __builtin_bit_cast(u32x4s, h8), mm = __builtin_bit_cast(u32x4s, m8), ll = __builtin_bit_cast(u32x4s, l8);
-                        d[0] = u32x2s{hh[0], hh[1]};
-                        d[CPL * 2] = u32x2s{mm[0], mm[1]};
-                        d[2 * CPL * 2] = u32x2s{ll[0], ll[1]};
+                        for (int r = 0; r < 4; ++r) v[r] = inside ? fmaxf(fmaf(acc[r], sc1[r], sh1[r]), 0.0f) : 0.0f;
+                        dmvs_store_split4(v, reinterpret_cast<dmvs_u32x2*>(s_c0) + ((cl & 7) * CW + pc) * 2 + (kq & 1), CPL * 2);
                     }
                 }
             }
@@ -295,12 +252,7 @@ featurenet_stem3_kernel(const float* __restrict__ x, const float* __restrict__ w
                 for (int s = 0; s < K2S; ++s) {
                     if (s + 2 < K2S) fetch(s + 2);
                     __builtin_amdgcn_sched_barrier(0);
-                    acc = dmvs_mfma_bf16(pl[s], w2h[s], acc);
-                    acc = dmvs_mfma_bf16(ph[s], w2l[s], acc);
-                    acc = dmvs_mfma_bf16(pmid[s], w2m[s], acc);
-                    acc = dmvs_mfma_bf16(pmid[s], w2h[s], acc);
-                    acc = dmvs_mfma_bf16(ph[s], w2m[s], acc);
-                    acc = dmvs_mfma_bf16(ph[s], w2h[s], acc);
+                    dmvs_split_step<1, true>(&ph[s], &pmid[s], &pl[s], w2h[s], w2m[s], w2l[s], &acc);
                     __builtin_amdgcn_sched_barrier(0);
                 }
                 // D[row = pixel 4*kq + r][col = cout m]: 4 consecutive pixels of one (row, channel)

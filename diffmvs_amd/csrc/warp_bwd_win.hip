@@ -81,7 +81,7 @@ getcost_bwd_win_kernel(const dmvs_getcost_desc d, const float* __restrict__ gcos
                 if (dch[i] < NCH && dcol[i] < ncols) {
                     const float* srcp = rowp + dcol[i] * C + dch[i] * 4;
                     float* dstp = win + (r * SLOTS + i * 64) * 4;
-                    __builtin_amdgcn_global_load_lds(srcp, DMVS_LDS3(dstp), 16, 0, 0);
+                    __builtin_amdgcn_global_load_lds(srcp, DMVS_LDS_PTR(dstp), 16, 0, 0);
                 }
             }
         }

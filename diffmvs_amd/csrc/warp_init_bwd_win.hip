@@ -171,7 +171,7 @@ warp_init_bwd_win_kernel(const float* __restrict__ ref, const float* __restrict_
                         if (dch[i] < NCH && dcol[i] < ncols) {
                             const float* srcp = rowp + dcol[i] * C + dch[i] * 4;
                             float* dstp = win + (r * SLOTS + i * 64) * 4;
-                            __builtin_amdgcn_global_load_lds(srcp, DMVS_LDS3(dstp), 16, 0, 0);
+                            __builtin_amdgcn_global_load_lds(srcp, DMVS_LDS_PTR(dstp), 16, 0, 0);
                         }
                     }
                 }

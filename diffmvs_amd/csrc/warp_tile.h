@@ -12,8 +12,6 @@ constexpr int TW = 16, TH = 16;      // reference-pixel tile of a workgroup (one
 constexpr int WW = 24;               // window width in texels
 template <int C> struct WinCfg { static constexpr int WH = C == 32 ? 22 : 24; };   // rows: 76 KB (C=32) / 46 KB (C=16)
 
-#define DMVS_LDS3(p) ((__attribute__((address_space(3))) void*)(p))
-
 struct RayW {
     float rx, ry, rz, tx, ty, tz;
     __device__ __forceinline__ void init(const float* m, float x, float y) {
