@@ -111,6 +111,9 @@ SIGNATURES = {
     "dmvs_tsdf_flags_u8": [_P, _P, _I, _I, _I, _I, _P, _P, _P],
     "dmvs_tsdf_vertices_f32": [_P, _P, _P, _I, _I, _I, _P, C.c_double, _P, _P, C.c_int64, _P, _P, _P],
     "dmvs_tsdf_faces_i32": [_P, _I, _I, _I, _P, _P, _P, C.c_int64, _P, _P],
+    "dmvs_mesh_raster_fill_u64": [_P, C.c_int64, _P],
+    "dmvs_mesh_raster_zid_u64": [_P, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64, _I, _I, _I, _I, _P, _P, _P, _P, C.c_int64, _P],
+    "dmvs_mesh_raster_resolve_f32": [_P, _P, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64, _I, _I, _P, _P, _P, _P, _P, _P],
 }
 VIEW_SELECT_MAX_IMAGES, VIEW_SELECT_MAX_LIST = 16384, 1 << 23      # dmvs.h: DMVS_VIEW_SELECT_MAX_IMAGES, DMVS_VIEW_SELECT_MAX_LIST
 CLOUD_MAX_RINGS, CLOUD_MAX_KEY_BITS, CLOUD_MAX_THRESHOLDS = 1024, 62, 16      # dmvs.h: DMVS_CLOUD_MAX_*
@@ -119,6 +122,7 @@ DEPTH_MAX_THRESHOLDS, DEPTH_SLOTS = 8, 7      # dmvs.h: DMVS_DEPTH_MAX_THRESHOLD
 SPLAT_VIEW_CHUNK, SPLAT_VIEW_DOUBLES, SPLAT_SLOTS, SPLAT_MAX_RADIUS, SPLAT_NO_PRETEST = 8, 15, 4, 16, 0x1      # dmvs.h: DMVS_SPLAT_*
 NORMAL_MAX_RADIUS, NORMAL_CAM_DOUBLES, NORMAL_VIEW_CHUNK, NORMAL_SLOTS = 4, 27, 8, 4      # dmvs.h: DMVS_NORMAL_*
 TSDF_VIEW_CHUNK, TSDF_VIEW_DOUBLES, TSDF_MAX_VIEWS, TSDF_MAX_QUADS, TSDF_NO_CULL = 8, 12, 65535, 357913941, 0x1      # dmvs.h: DMVS_TSDF_*
+RASTER_VIEW_DOUBLES, RASTER_SLOTS, RASTER_SMALL, RASTER_CULL_NEG, RASTER_CULL_POS = 22, 8, 64, 0x1, 0x2      # dmvs.h: DMVS_RASTER_*
 ABI_VERSION = 4
 # dmvs.h: DMVS_TUNE_* (dmvs_conv2d_desc.tune, dmvs_featurenet_stem_f32), DMVS_TUNE3D_* (dmvs_conv3d_desc.tune), DMVS_TUNE_SWEEP_GLOBAL
 TUNE_NO_WALK, TUNE_PIECES4, TUNE_NO_LEAN, TUNE_1X1_TILED, TUNE_NO_TALL, TUNE_TALL = 0x4, 0x8, 0x100, 0x200, 0x400, 0x800

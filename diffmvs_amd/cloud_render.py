@@ -151,23 +151,42 @@ def _moved(pts: torch.Tensor, transform) -> torch.Tensor:
 
 
 # ------------------------------------------------------------------------------------------ trees
-def render_scene(ops, cloud, tree: str, out: str, dataset: str, scan: str, transform=None, **kw) -> dict:
-    """one scan of the tree: every reference view of its pair.txt, grouped by image size -> the render.json record.  REPLACES the .pfm / .png
-    files of <out>/<scan>/depth_gt and mask (the command line refuses beforehand unless --overwrite)"""
-    from PIL import Image
+def scene_views(tree: str, out: str, dataset: str, scan: str):
+    """the reference views of one scan's pair.txt, grouped by image size -> (base, {(H, W): [(view id, K, E, depth_min, depth_max), ...]});
+    base is where the scan's depth_gt/, mask/ and render.json go"""
     ds = IO.MVSDataset(tree, dataset=dataset, scan=[scan])
     base = os.path.join(out, scan) if dataset != "general" else out
-    ddir, mdir = os.path.join(base, "depth_gt"), os.path.join(base, "mask")
-    ids = sorted({ref for _, ref, _ in ds.metas})
     groups = {}
-    for vid in ids:
+    for vid in sorted({ref for _, ref, _ in ds.metas}):
         img, k, e, d0, d1 = ds.load_view(scan, vid)
         groups.setdefault(img.shape[:2], []).append((vid, k, e, d0, d1))
-    for d, ext in ((ddir, ".pfm"), (mdir, ".png")):              # (main has refused by now unless --overwrite: maps of views that are
-        os.makedirs(d, exist_ok=True)                            # no longer in pair.txt must not survive beside the new render.json)
+    return base, groups
+
+
+def clear_maps(base: str):
+    """-> (depth_gt/, mask/) of `base`, made and emptied of .pfm / .png files (main has refused by now unless --overwrite: maps of views
+    that are no longer in pair.txt must not survive beside the new render.json)"""
+    ddir, mdir = os.path.join(base, "depth_gt"), os.path.join(base, "mask")
+    for d, ext in ((ddir, ".pfm"), (mdir, ".png")):
+        os.makedirs(d, exist_ok=True)
         for f in os.listdir(d):
             if f.endswith(ext):
                 os.remove(os.path.join(d, f))
+    return ddir, mdir
+
+
+def write_maps(ddir: str, mdir: str, vid: int, depth: np.ndarray) -> None:
+    """depth_gt/%08d.pfm and mask/%08d.png (0 / 255 where depth > 0) of one view"""
+    from PIL import Image
+    IO.save_pfm(os.path.join(ddir, f"{vid:08d}.pfm"), depth)
+    Image.fromarray(np.where(depth > 0, 255, 0).astype(np.uint8)).save(os.path.join(mdir, f"{vid:08d}.png"))
+
+
+def render_scene(ops, cloud, tree: str, out: str, dataset: str, scan: str, transform=None, **kw) -> dict:
+    """one scan of the tree: every reference view of its pair.txt, grouped by image size -> the render.json record.  REPLACES the .pfm / .png
+    files of <out>/<scan>/depth_gt and mask (the command line refuses beforehand unless --overwrite)"""
+    base, groups = scene_views(tree, out, dataset, scan)
+    ddir, mdir = clear_maps(base)
     record = {"scan": scan, "mode": kw.get("mode", "mean"), "views": {}}
     for (H, W), views in groups.items():
         res = render_depth(ops, cloud, np.stack([v[1] for v in views]), np.stack([v[2] for v in views]), (H, W),
@@ -175,8 +194,7 @@ def render_scene(ops, cloud, tree: str, out: str, dataset: str, scan: str, trans
         depth, counts = res["depth"].cpu().numpy(), res["counts"].cpu().tolist()
         record["radius"] = res["radius"]
         for i, (vid, *_rest) in enumerate(views):
-            IO.save_pfm(os.path.join(ddir, f"{vid:08d}.pfm"), depth[i])
-            Image.fromarray(np.where(depth[i] > 0, 255, 0).astype(np.uint8)).save(os.path.join(mdir, f"{vid:08d}.png"))
+            write_maps(ddir, mdir, vid, depth[i])
             record["views"][f"{vid:08d}"] = {"size": [H, W], "non_finite": counts[i][0], "outside_depth_range": counts[i][1], "off_image": counts[i][2],
                                              "radius_clamped": counts[i][3], "covered": float((depth[i] > 0).mean()), "radius": res["radius"]}
     with open(os.path.join(base, "render.json"), "w") as f:
@@ -184,30 +202,25 @@ def render_scene(ops, cloud, tree: str, out: str, dataset: str, scan: str, trans
     return record
 
 
-def main(argv=None, ops=None) -> dict:
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--cloud", required=True, help="the ground-truth cloud (PLY)")
+def add_tree_arguments(ap, what: str) -> None:
+    """the options every renderer of a tree shares (cloud_render, mesh_render)"""
     ap.add_argument("--tree", required=True, help="the MVS tree whose views are rendered (formats.MVSDataset layout)")
     ap.add_argument("--dataset", default="general", choices=["dtu", "tank", "eth3d", "general"])
     ap.add_argument("--testlist", default=None, help="file with one scan per line (dtu / tank / eth3d)")
-    ap.add_argument("--transform", default=None, help="4x4 text file as cloud_register writes it: applied to the cloud first")
-    ap.add_argument("--invert", action="store_true", help="apply the inverse of --transform (a ground-truth cloud into the tree's frame)")
+    ap.add_argument("--transform", default=None, help=f"4x4 text file as cloud_register writes it: applied to the {what} first")
+    ap.add_argument("--invert", action="store_true", help=f"apply the inverse of --transform (a ground-truth {what} into the tree's frame)")
     ap.add_argument("--out", default=None, help="where depth_gt/, mask/ and render.json go (default: the tree itself)")
-    ap.add_argument("--mode", default="mean", choices=["mean", "nearest"])
-    ap.add_argument("--radius", type=float, default=None, help="world-space half-width of a splat (default: the cloud's point spacing)")
-    ap.add_argument("--r_min", type=float, default=0.5)
-    ap.add_argument("--r_max", type=float, default=8.0)
-    ap.add_argument("--tau", type=float, default=0.01, help="mean mode: points within (1 + tau) of a pixel's nearest depth are averaged")
     ap.add_argument("--overwrite", action="store_true")
     ap.add_argument("--device", default="cuda:0")
-    a = ap.parse_args(argv)
-    if ops is None:
-        from .ops import Ops
-        ops = Ops.for_device(a.device)
+
+
+def tree_arguments(a, prog: str):
+    """-> (scans, transform or None, out) of the parsed options of add_tree_arguments.  Refuses BEFORE anything is written: no scan may
+    already hold a depth_gt/ unless --overwrite"""
     scans = [""]
     if a.dataset != "general":
         if not a.testlist:
-            raise SystemExit(f"cloud_render: --dataset {a.dataset} keeps one directory per scan: name them with --testlist")
+            raise SystemExit(f"{prog}: --dataset {a.dataset} keeps one directory per scan: name them with --testlist")
         with open(a.testlist) as f:
             scans = [ln.strip() for ln in f if ln.strip()]
     T = None
@@ -216,14 +229,30 @@ def main(argv=None, ops=None) -> dict:
         T = load_transform(a.transform)
         T = np.linalg.inv(T) if a.invert else T
     elif a.invert:
-        raise SystemExit("cloud_render: --invert needs --transform")
-    cloud = G.to_cloud(ops, IO.read_ply(a.cloud)[0])
+        raise SystemExit(f"{prog}: --invert needs --transform")
     out = a.out or a.tree
-    # refuse BEFORE anything is written: no scan may already hold a depth_gt/
     for scan in scans:
         ddir = os.path.join(out, scan, "depth_gt") if a.dataset != "general" else os.path.join(out, "depth_gt")
         if os.path.isdir(ddir) and os.listdir(ddir) and not a.overwrite:
-            raise SystemExit(f"cloud_render: {ddir} exists; pass --overwrite to replace it")
+            raise SystemExit(f"{prog}: {ddir} exists; pass --overwrite to replace it")
+    return scans, T, out
+
+
+def main(argv=None, ops=None) -> dict:
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--cloud", required=True, help="the ground-truth cloud (PLY)")
+    add_tree_arguments(ap, "cloud")
+    ap.add_argument("--mode", default="mean", choices=["mean", "nearest"])
+    ap.add_argument("--radius", type=float, default=None, help="world-space half-width of a splat (default: the cloud's point spacing)")
+    ap.add_argument("--r_min", type=float, default=0.5)
+    ap.add_argument("--r_max", type=float, default=8.0)
+    ap.add_argument("--tau", type=float, default=0.01, help="mean mode: points within (1 + tau) of a pixel's nearest depth are averaged")
+    a = ap.parse_args(argv)
+    if ops is None:
+        from .ops import Ops
+        ops = Ops.for_device(a.device)
+    scans, T, out = tree_arguments(a, "cloud_render")
+    cloud = G.to_cloud(ops, IO.read_ply(a.cloud)[0])
     res = {"cloud": a.cloud, "points": int(cloud.shape[0]), "scans": {}}
     for scan in scans:
         res["scans"][scan] = render_scene(ops, cloud, a.tree, out, a.dataset, scan, transform=T, radius=a.radius,

@@ -227,6 +227,24 @@ __device__ __forceinline__ unsigned dmvs_peek_u32(const unsigned* p) {
 #endif
 }
 
+// The same pair on 64 bits, for the rasteriser's (depth bits << 32 | face) keys (mesh_render.hip).
+__device__ __forceinline__ void dmvs_atomic_min_u64(unsigned long long* p, unsigned long long v) {
+#ifdef DMVS_HOST_EMULATION
+    unsigned long long old = __atomic_load_n(p, __ATOMIC_RELAXED);
+    while (v < old && !__atomic_compare_exchange_n(p, &old, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {
+    }
+#else
+    atomicMin(p, v);
+#endif
+}
+__device__ __forceinline__ unsigned long long dmvs_peek_u64(const unsigned long long* p) {
+#ifdef DMVS_HOST_EMULATION
+    return __atomic_load_n(p, __ATOMIC_RELAXED);
+#else
+    return *p;
+#endif
+}
+
 // host side of such a launch: the scale is a positive finite power of two ...
 inline bool cloud_pow2(double s) {
     int e = 0;

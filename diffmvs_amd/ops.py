@@ -146,6 +146,7 @@ def _ptr(t: Optional[torch.Tensor]):
 
 
 MAX_WINDOW_VIEWS = 16      # include/dmvs.h: DMVS_GETCOST_MAX_WINDOW_VIEWS
+RASTER_QUEUE_ENTRIES = 1 << 20      # mesh_raster_zid: the default queue of large (face, view) pairs holds at most this many (8 MiB)
 
 # Kernels that write parameters / buffers through raw pointers (dmvs_adamw_step_f32, the running statistics of
 # dmvs_batchnorm_train_fwd_f32) do not bump torch's per-tensor version counters, so every cache of packed weights
@@ -1138,6 +1139,61 @@ class Ops:
         if Q > 0:
             self._call("dmvs_tsdf_faces_i32", _ptr(vol.S), nx, ny, nz, _ptr(quad), _ptr(quad_cum), _ptr(cell_cum), Q, _ptr(faces), self.stream())
         return verts, rgb, faces
+
+    # ------------------------------------------------------------------ triangle meshes into the views (diffmvs_amd/mesh_render.py)
+    def _raster_args(self, what, verts, faces, views):
+        """the checks both raster passes share -> (N, F, V, the HOST view table)"""
+        import numpy as np
+        self._chk_typed(what, (verts, torch.float32), (faces, torch.int32))
+        if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+            raise _lib.DmvsError(f"{what}: verts must be [N,3] and faces [F,3], got {tuple(verts.shape)} and {tuple(faces.shape)}")
+        v = np.ascontiguousarray(views.detach().cpu().numpy() if torch.is_tensor(views) else views, dtype=np.float64)
+        if v.ndim != 2 or v.shape[1] != _lib.RASTER_VIEW_DOUBLES:
+            raise _lib.DmvsError(f"{what}: views must be [V,{_lib.RASTER_VIEW_DOUBLES}] (two rows of P, E[:3], near, far), got {v.shape}")
+        return int(verts.shape[0]), int(faces.shape[0]), int(v.shape[0]), v
+
+    def mesh_raster_zid(self, verts, faces, views, size, cull=None, transform=None, zid=None, queue_cap=None, blocks=0, work=False):
+        """dmvs_mesh_raster_fill_u64 / dmvs_mesh_raster_zid_u64 (include/dmvs.h): per pixel the smallest (depth bits << 32 | face) of the
+        faces that cover it.  verts [N,3] fp32, faces [F,3] int32; views [V,22] fp64 on the host (mesh_render.view_table); size (H, W);
+        cull None | "neg" | "pos"; zid: None (a fresh [V,H,W] buffer of all ones) or one to go on with, int64 holding the uint64 keys;
+        queue_cap: entries of the wave pass's queue, None = one per (face, view) of a launch up to RASTER_QUEUE_ENTRIES, 0 = no wave pass.
+        -> (zid, counts [V,8] int64[, work [3] int64: covered pixels, atomics issued, faces that fell back])"""
+        N, F, V, v = self._raster_args("mesh_raster_zid", verts, faces, views)
+        H, W = int(size[0]), int(size[1])
+        if cull not in (None, "neg", "pos"):
+            raise _lib.DmvsError(f"mesh_raster_zid: cull must be None, 'neg' or 'pos', got {cull!r}")
+        flags = {None: 0, "neg": _lib.RASTER_CULL_NEG, "pos": _lib.RASTER_CULL_POS}[cull]
+        if zid is None:
+            zid = torch.empty((V, H, W), dtype=torch.int64, device=self.device)
+            self._call("dmvs_mesh_raster_fill_u64", _ptr(zid), zid.numel(), self.stream())
+        elif zid.dtype != torch.int64 or tuple(zid.shape) != (V, H, W) or not zid.is_contiguous() or zid.device != self.device:
+            raise _lib.DmvsError(f"mesh_raster_zid: zid must be a contiguous int64 [V,H,W] = {(V, H, W)} on {self.device}")
+        if queue_cap is None:
+            queue_cap = min(F * min(V, _lib.SPLAT_VIEW_CHUNK), RASTER_QUEUE_ENTRIES)
+        queue = torch.empty(1 + int(queue_cap), dtype=torch.int64, device=self.device) if queue_cap > 0 else None
+        counts = torch.empty((V, _lib.RASTER_SLOTS), dtype=torch.int64, device=self.device)
+        wk = torch.empty((3,), dtype=torch.int64, device=self.device) if work else None
+        self._call("dmvs_mesh_raster_zid_u64", _ptr(verts), N, _ptr(faces), F, self._transform_arg(transform), v.ctypes.data_as(C.c_void_p), V, H, W,
+                   flags, int(blocks), _ptr(zid), _ptr(counts), _ptr(wk), _ptr(queue), int(queue_cap), self.stream())
+        return (zid, counts, wk) if work else (zid, counts)
+
+    def mesh_raster_resolve(self, zid, verts, faces, views, transform=None, vrgb=None, normals=False):
+        """dmvs_mesh_raster_resolve_f32 (include/dmvs.h) over the finished zid of mesh_raster_zid (same mesh, transform and views).
+        -> (depth [V,H,W] fp32, 0 where nothing was drawn; face [V,H,W] int32, -1 there; normal [V,H,W,3] fp32 or None: the winning
+        face's unit normal in the world frame, turned to the camera; rgb [V,H,W,3] uint8 or None: vrgb [N,3] uint8 interpolated)"""
+        N, F, V, v = self._raster_args("mesh_raster_resolve", verts, faces, views)
+        self._chk_typed("mesh_raster_resolve", (zid, torch.int64), (vrgb, torch.uint8))
+        if zid.dim() != 3 or zid.shape[0] != V or (vrgb is not None and tuple(vrgb.shape) != (N, 3)):
+            raise _lib.DmvsError(f"mesh_raster_resolve: zid must be [V,H,W] with V = {V} and vrgb [N,3], got {tuple(zid.shape)}"
+                                 + (f" and {tuple(vrgb.shape)}" if vrgb is not None else ""))
+        H, W = int(zid.shape[1]), int(zid.shape[2])
+        depth = torch.empty((V, H, W), dtype=torch.float32, device=self.device)
+        face = torch.empty((V, H, W), dtype=torch.int32, device=self.device)
+        normal = torch.empty((V, H, W, 3), dtype=torch.float32, device=self.device) if normals else None
+        rgb = torch.empty((V, H, W, 3), dtype=torch.uint8, device=self.device) if vrgb is not None else None
+        self._call("dmvs_mesh_raster_resolve_f32", _ptr(zid), _ptr(verts), N, _ptr(faces), F, self._transform_arg(transform),
+                   v.ctypes.data_as(C.c_void_p), V, H, W, _ptr(vrgb), _ptr(depth), _ptr(face), _ptr(normal), _ptr(rgb), self.stream())
+        return depth, face, normal, rgb
 
 
 class TsdfVolume:

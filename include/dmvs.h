@@ -792,6 +792,68 @@ int dmvs_tsdf_vertices_f32(const int32_t* S, const int32_t* Wt, const uint32_t* 
 int dmvs_tsdf_faces_i32(const int32_t* S, int32_t nx, int32_t ny, int32_t nz, const uint8_t* quad, const int32_t* quad_cum,
                         const int32_t* cell_cum, int64_t Q, int32_t* faces, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Triangle meshes into the views (added under ABI 4, additive; diffmvs_amd/mesh_render.py): a z-buffer rasteriser whose coverage is
+ * exact integer arithmetic on vertices snapped to 1/256 pixel.  Integer min and integer adds only: zid and counts are bitwise
+ * independent of blocks, of the queue, of the launch order and of the order of the faces.
+ *
+ * verts [N,3] fp32, faces [F,3] int32 (device).  transform: as above (HOST 3x4 or NULL), applied to a vertex first; the moved vertex
+ * is fp32.  views: HOST [V, DMVS_RASTER_VIEW_DOUBLES] doubles per view: rows 0 and 1 of P = K E[:3] (4 + 4), E[:3] row-major (12,
+ * world -> camera), near, far.  Views go DMVS_SPLAT_VIEW_CHUNK per launch as kernel arguments.
+ *
+ * dmvs_mesh_raster_fill_u64: zid[0 .. n) = all ones ("nothing drawn") on the stream.
+ *
+ * dmvs_mesh_raster_zid_u64: zid [V,H,W] uint64 is the CALLER's, pre-filled with all ones.  Every (face, view) is counted in exactly
+ * one slot of counts [V, DMVS_RASTER_SLOTS] int64 (device, zeroed here).  IEEE fp64 in exactly this order, no contraction:
+ *   1. per vertex (X, Y, Z) widened to fp64:  x = ((P00 X + P01 Y) + P02 Z) + P03,  y likewise with row 1,
+ *      z = ((E20 X + E21 Y) + E22 Z) + E23,  u = x / z,  v = y / z  (pixel centres at integer coordinates)
+ *   2. slot 0: a vertex index outside [0, N) or a (moved) coordinate that is not finite
+ *   3. slot 1: some vertex has z <= near.  The face is NOT DRAWN -- there is no near clipping; the count tells the caller
+ *   4. slot 2: all three vertices have z > far
+ *   5. slot 3: some |u| or |v| is not <= 2^20 (the guard band; NaN included)
+ *   6. sx = llrint(u * 256), sy = llrint(v * 256) as int64; everything about coverage is integer arithmetic from here (below 2^59)
+ *   7. A = (sx1 - sx0)(sy2 - sy0) - (sy1 - sy0)(sx2 - sx0);  slot 4: A == 0;  slot 5: culled (flags & DMVS_RASTER_CULL_NEG and A < 0,
+ *      or flags & DMVS_RASTER_CULL_POS and A > 0);  if A < 0, vertices 1 and 2 change places and A = -A (the face keeps its index)
+ *   8. columns max(ceil(min sx / 256), 0) .. min(floor(max sx / 256), W - 1), rows likewise with sy and H;  slot 6: the box is empty;
+ *      otherwise slot 7: drawn
+ *   9. pixel (px, py) of the box is COVERED iff for k = 0, 1, 2, with a = k + 1, b = k + 2 (mod 3), dx = sxb - sxa, dy = syb - sya,
+ *      e_k = dx (256 py - sya) - dy (256 px - sxa):   e_k > 0,  or  e_k == 0 and (dy > 0 or (dy == 0 and dx > 0)).
+ *      Of the two directions of a shared edge exactly one owns its boundary: a pixel centre on it belongs to one of the two faces
+ *  10. wq_k = ((double)e_k / (double)A) * (1.0 / z_k);  zp = 1.0 / ((wq_0 + wq_1) + wq_2);  skipped unless zp <= far;
+ *      zid[pixel] = min(zid[pixel], (uint64)bits((float)zp) << 32 | face): one u64 integer atomic-min, behind a plain load that skips
+ *      it when it cannot lower the pixel.  The depth is positive, so the bits order like the values; equal depths go to the smaller face
+ *   work: NULL or [3] uint64 (device, zeroed here): covered pixels (exact), atomics issued (depends on timing), faces that fell back.
+ *   A (face, view) whose box holds at most DMVS_RASTER_SMALL pixels is walked by the lane that projected it.  A larger one is appended
+ *   to `queue` -- the caller's [1 + queue_cap] uint64 on the device, word 0 the counter, zeroed here per launch -- and walked by a whole
+ *   wave in a second launch; with the queue full (or queue_cap = 0) the lane walks it itself and work[2] counts it.
+ *   blocks: workgroups of the grid-stride launches, 0 = the library's choice.
+ *
+ * dmvs_mesh_raster_resolve_f32: per pixel of the FINISHED zid (same mesh, transform and views).  depth [V,H,W] fp32 = the high word
+ * as a float, face [V,H,W] int32 = the low word; 0 and -1 where zid is all ones.
+ *   normal: NULL or [V,H,W,3] fp32, from the winning face's (moved) vertices p0, p1, p2 in the order of the file, widened to fp64:
+ *     a = p1 - p0, b = p2 - p0, c = (ay bz - az by, az bx - ax bz, ax by - ay bx), len = sqrt((cx^2 + cy^2) + cz^2), n = c / len;
+ *     with nc_i = (Ei0 nx + Ei1 ny) + Ei2 nz and pc_i = ((Ei0 X0 + Ei1 Y0) + Ei2 Z0) + Ei3:  n = -n if (nc_0 pc_0 + nc_1 pc_1) + nc_2 pc_2 > 0
+ *     (it faces the camera); rounded once to fp32.  Zeros where nothing was drawn or len is 0 or not finite.
+ *   rgb: NULL or [V,H,W,3] uint8 from vrgb [N,3] uint8: steps 1 to 10 redone for that face and pixel, b_k = wq_k * zp, a channel is
+ *     fmin(fmax(rint((b_0 c_0 + b_1 c_1) + b_2 c_2), 0), 255) with c_k the (swapped) vertices' values.  Zeros where nothing was drawn.
+ *
+ * F = 0 or V = 0: nothing but the zeroed counters is touched.  DMVS_EINVAL (before any launch): a negative size, N, F or H W >= 2^31,
+ * V H W > 2^40, NULL operands with work to do, verts / faces / depth / face / normal not 4-byte or zid / counts / work / queue not
+ * 8-byte aligned, a non-finite views entry, near <= 0, far <= near or far > FLT_MAX, both cull flags or an unknown one, blocks < 0,
+ * queue_cap < 0 or >= 2^31, a NULL queue with queue_cap > 0, a non-finite transform, rgb without vrgb. */
+#define DMVS_RASTER_VIEW_DOUBLES 22
+#define DMVS_RASTER_SLOTS 8
+#define DMVS_RASTER_SMALL 64
+#define DMVS_RASTER_CULL_NEG 0x1
+#define DMVS_RASTER_CULL_POS 0x2
+int dmvs_mesh_raster_fill_u64(uint64_t* zid, int64_t n, void* stream);
+int dmvs_mesh_raster_zid_u64(const float* verts, int64_t N, const int32_t* faces, int64_t F, const double* transform, const double* views,
+                             int64_t V, int32_t H, int32_t W, int32_t flags, int32_t blocks, uint64_t* zid, int64_t* counts,
+                             uint64_t* work, uint64_t* queue, int64_t queue_cap, void* stream);
+int dmvs_mesh_raster_resolve_f32(const uint64_t* zid, const float* verts, int64_t N, const int32_t* faces, int64_t F, const double* transform,
+                                 const double* views, int64_t V, int32_t H, int32_t W, const uint8_t* vrgb, float* depth, int32_t* face,
+                                 float* normal, uint8_t* rgb, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
