@@ -114,6 +114,9 @@ SIGNATURES = {
     "dmvs_mesh_raster_fill_u64": [_P, C.c_int64, _P],
     "dmvs_mesh_raster_zid_u64": [_P, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64, _I, _I, _I, _I, _P, _P, _P, _P, C.c_int64, _P],
     "dmvs_mesh_raster_resolve_f32": [_P, _P, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64, _I, _I, _P, _P, _P, _P, _P, _P],
+    "dmvs_mesh_label_round_i32": [_P, C.c_int64, C.c_int64, _P, _P, _I, _P],
+    "dmvs_mesh_face_tally_i64": [_P, C.c_int64, _P, C.c_int64, _P, C.c_double, C.c_double, _P, _P, _P, _I, _P],
+    "dmvs_mesh_sample_f32": [_P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int64, _P, _P, _I, _P],
 }
 VIEW_SELECT_MAX_IMAGES, VIEW_SELECT_MAX_LIST = 16384, 1 << 23      # dmvs.h: DMVS_VIEW_SELECT_MAX_IMAGES, DMVS_VIEW_SELECT_MAX_LIST
 CLOUD_MAX_RINGS, CLOUD_MAX_KEY_BITS, CLOUD_MAX_THRESHOLDS = 1024, 62, 16      # dmvs.h: DMVS_CLOUD_MAX_*

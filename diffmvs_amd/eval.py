@@ -140,6 +140,10 @@ def main(argv=None, device=None):
     ap.add_argument("--mesh_resolution", type=int, default=512, help="--mesh, without --mesh_voxel: voxels along the longest axis of the scene's box")
     ap.add_argument("--mesh_trunc", type=float, default=4.0, help="--mesh: truncation distance in voxels")
     ap.add_argument("--mesh_min_weight", type=int, default=2, help="--mesh: a voxel counts as observed from this many views on")
+    ap.add_argument("--mesh_min_component", type=int, default=0, help="--mesh: drop connected components with fewer faces (floaters) before the mesh is written "
+                    "(diffmvs_amd.mesh_clean); mesh[scene] gains `cleaned`")
+    ap.add_argument("--mesh_score", type=float, default=None, metavar="SPACING", help="--mesh with --gt_ply: also score the mesh, sampled at one point per SPACING^2 of "
+                    "area, with the cloud's transform, crop, max distance and thresholds (diffmvs_amd.mesh_eval); adds mesh_eval[scene] to the result")
     ap.add_argument("--gt_ply", default=None, help="with --filter: score every fused cloud against this ground-truth PLY ('{scene}' is substituted) "
                     "with diffmvs_amd.cloud_eval; adds cloud_metrics[scene] to the result")
     ap.add_argument("--gt_transform", default=None, help="--gt_ply: 4x4 text file that moves the fused cloud into the ground truth's frame ('{scene}' is substituted)")
@@ -210,7 +214,7 @@ def main(argv=None, device=None):
                 from . import mesh
                 res.setdefault("mesh", {})[scene] = mesh.mesh_scene(
                     os.path.join(a.outdir, scene), os.path.join(a.testpath, scene), a.dataset, voxel=a.mesh_voxel, resolution=a.mesh_resolution,
-                    trunc=a.mesh_trunc, min_weight=a.mesh_min_weight, device=device)
+                    trunc=a.mesh_trunc, min_weight=a.mesh_min_weight, device=device, min_component_faces=a.mesh_min_component)
             if a.gt_ply:
                 from . import cloud_eval, cloud_register
                 extra = {}
@@ -221,6 +225,11 @@ def main(argv=None, device=None):
                 res.setdefault("cloud_metrics", {})[scene] = cloud_eval.evaluate_files(
                     Ops.for_device(device), kw["plyfilename"], a.gt_ply.replace("{scene}", scene), a.cloud_max_dist, a.cloud_thresholds,
                     density=a.cloud_density, **extra)
+                if a.mesh and a.mesh_score is not None:
+                    from . import mesh_eval
+                    res.setdefault("mesh_eval", {})[scene] = mesh_eval.evaluate_files(
+                        Ops.for_device(device), res["mesh"][scene]["ply"], a.gt_ply.replace("{scene}", scene), a.mesh_score, a.cloud_max_dist,
+                        a.cloud_thresholds, **extra)
     if a.gt_depth:
         from . import depth_eval
         from .ops import Ops

@@ -2,7 +2,7 @@
 over its zero set (dmvs_tsdf_* of include/dmvs.h, csrc/tsdf.hip; Ops.tsdf_integrate / Ops.tsdf_extract).
 
     python -m diffmvs_amd.mesh --outdir <eval output> [--testpath <root> --dataset dtu --testlist list.txt]
-        [--voxel S | --resolution N] [--trunc 4] [--min_weight 2] [--bounds x0 y0 z0 x1 y1 z1] [--out mesh.ply]
+        [--voxel S | --resolution N] [--trunc 4] [--min_weight 2] [--bounds x0 y0 z0 x1 y1 z1] [--out mesh.ply] [--min_component N]
 
 reads the tree diffmvs_amd.eval (--filter) leaves behind -- cams/, images/, depth_fused/ (fusion.filter_depth(write_fused=True): the
 depth averaged over the consistent views) or else depth_est/, and mask/*_final.png or else every finite positive depth -- and writes a
@@ -106,10 +106,12 @@ def scene_views(out_folder, pair_folder, dataset):
 
 
 def mesh_scene(out_folder, pair_folder=None, dataset="dtu", voxel=None, resolution=512, trunc=4.0, min_weight=2, bounds=None, out=None,
-               device="cuda:0", ops: Ops | None = None, chunk=_lib.TSDF_VIEW_CHUNK, max_voxels=2 ** 29, stride=4, colour=True) -> dict:
+               device="cuda:0", ops: Ops | None = None, chunk=_lib.TSDF_VIEW_CHUNK, max_voxels=2 ** 29, stride=4, colour=True,
+               min_component_faces=0) -> dict:
     """One scene's output tree -> <out_folder>/mesh.ply (or `out`).  The truncation distance is trunc voxels; bounds (x0 y0 z0 x1 y1 z1)
     default to auto_bounds widened by tau + h.  The views stream through the volume `chunk` at a time.
-    -> {"ply", "vertices", "faces", "dims", "voxel", "observed_voxels" (Wt >= min_weight), "views", "bounds"}"""
+    min_component_faces > 0: connected components with fewer faces are dropped before the file is written (mesh_clean.clean).
+    -> {"ply", "vertices", "faces", "dims", "voxel", "observed_voxels" (Wt >= min_weight), "views", "bounds"[, "cleaned"]}"""
     from PIL import Image
     ops = ops or Ops.for_device(device)
     dev = ops.device
@@ -156,12 +158,19 @@ def mesh_scene(out_folder, pair_folder=None, dataset="dtu", voxel=None, resoluti
                            tsdf_views(np.stack([w[3] for w in batch]), np.stack([w[4] for w in batch])), tau)
         i0 += len(batch)
     verts, rgb, faces = ops.tsdf_extract(vol, min_weight=min_weight)
+    cleaned = None
+    if int(min_component_faces) > 0:
+        from . import mesh_clean
+        verts, rgb, faces, cleaned = mesh_clean.clean(ops, verts, rgb, faces, min_faces=int(min_component_faces))
     out = out or os.path.join(out_folder, "mesh.ply")
     if os.path.dirname(out):
         os.makedirs(os.path.dirname(out), exist_ok=True)
     IO.write_ply(out, verts.cpu().numpy(), rgb.cpu().numpy(), faces=faces.cpu().numpy())
-    return {"ply": out, "vertices": int(verts.shape[0]), "faces": int(faces.shape[0]), "dims": list(vol.dims), "voxel": vol.h,
-            "observed_voxels": int((vol.Wt >= int(min_weight)).sum()), "views": len(ids), "bounds": [float(x) for x in np.concatenate([lo, hi])]}
+    res = {"ply": out, "vertices": int(verts.shape[0]), "faces": int(faces.shape[0]), "dims": list(vol.dims), "voxel": vol.h,
+           "observed_voxels": int((vol.Wt >= int(min_weight)).sum()), "views": len(ids), "bounds": [float(x) for x in np.concatenate([lo, hi])]}
+    if cleaned is not None:
+        res["cleaned"] = cleaned
+    return res
 
 
 def main(argv=None, device="cuda:0", ops=None):
@@ -176,6 +185,7 @@ def main(argv=None, device="cuda:0", ops=None):
     ap.add_argument("--min_weight", type=int, default=2, help="a voxel counts as observed from this many views on")
     ap.add_argument("--bounds", type=float, nargs=6, default=None, metavar=("x0", "y0", "z0", "x1", "y1", "z1"))
     ap.add_argument("--out", default=None, help="the PLY to write (default: <outdir>/<scene>/mesh.ply)")
+    ap.add_argument("--min_component", type=int, default=0, help="drop connected components with fewer faces (floaters) before writing")
     a = ap.parse_args(argv)
     scenes = [""]
     if a.testlist:
@@ -186,7 +196,8 @@ def main(argv=None, device="cuda:0", ops=None):
     res = {}
     for scene in scenes:
         res[scene] = mesh_scene(os.path.join(a.outdir, scene), os.path.join(a.testpath, scene) if a.testpath else None, a.dataset, voxel=a.voxel,
-                                resolution=a.resolution, trunc=a.trunc, min_weight=a.min_weight, bounds=a.bounds, out=a.out, device=device, ops=ops)
+                                resolution=a.resolution, trunc=a.trunc, min_weight=a.min_weight, bounds=a.bounds, out=a.out, device=device, ops=ops,
+                                min_component_faces=a.min_component)
     print(json.dumps({"mesh": res}), flush=True)
     return res
 

@@ -1195,6 +1195,58 @@ class Ops:
                    v.ctypes.data_as(C.c_void_p), V, H, W, _ptr(vrgb), _ptr(depth), _ptr(face), _ptr(normal), _ptr(rgb), self.stream())
         return depth, face, normal, rgb
 
+    # ------------------------------------------------------------------ cleaning and scoring a mesh (diffmvs_amd/mesh_clean.py, mesh_eval.py)
+    def _mesh_args(self, what, verts, faces):
+        self._chk_typed(what, (verts, torch.float32), (faces, torch.int32))
+        if (verts is not None and (verts.dim() != 2 or verts.shape[1] != 3)) or faces.dim() != 2 or faces.shape[1] != 3:
+            raise _lib.DmvsError(f"{what}: verts must be [N,3] and faces [F,3], got {None if verts is None else tuple(verts.shape)} and {tuple(faces.shape)}")
+
+    def mesh_label_round(self, faces, label, state=None, blocks=0):
+        """dmvs_mesh_label_round_i32 (include/dmvs.h): one hook + shortcut round on label [N] int32 (label[v] = v before the first), in
+        place.  state: None or an int32 [2] to write.  -> state (device): atomics issued (0: the labels are final), out-of-range faces"""
+        self._mesh_args("mesh_label_round", None, faces)
+        self._chk_typed("mesh_label_round", (label, torch.int32), (state, torch.int32))
+        if label.dim() != 1 or (state is not None and tuple(state.shape) != (2,)):
+            raise _lib.DmvsError(f"mesh_label_round: label must be [N] and state [2], got {tuple(label.shape)}"
+                                 + (f" and {tuple(state.shape)}" if state is not None else ""))
+        if state is None:
+            state = torch.empty((2,), dtype=torch.int32, device=self.device)
+        self._call("dmvs_mesh_label_round_i32", _ptr(faces), int(faces.shape[0]), int(label.shape[0]), _ptr(label), _ptr(state), int(blocks), self.stream())
+        return state
+
+    def mesh_face_tally(self, verts, faces, label, scale, cap, blocks=0):
+        """dmvs_mesh_face_tally_i64 (include/dmvs.h): label [N] int32 (mesh_label_round's fixpoint); scale: a power of two; cap: the bound of
+        one face's scaled area.  -> (area_q [F] int64, comp_faces [N] int32, comp_area [N] int64; the sums sit at the components' roots)"""
+        self._mesh_args("mesh_face_tally", verts, faces)
+        self._chk_typed("mesh_face_tally", (label, torch.int32))
+        N, F = int(verts.shape[0]), int(faces.shape[0])
+        if tuple(label.shape) != (N,):
+            raise _lib.DmvsError(f"mesh_face_tally: label must be [N] = [{N}], got {tuple(label.shape)}")
+        fresh = torch.empty if N > 0 else torch.zeros      # (with no vertices the library touches nothing: every face is out of range)
+        area_q = fresh((F,), dtype=torch.int64, device=self.device)
+        comp_faces = torch.empty((N,), dtype=torch.int32, device=self.device)
+        comp_area = torch.empty((N,), dtype=torch.int64, device=self.device)
+        self._call("dmvs_mesh_face_tally_i64", _ptr(verts), N, _ptr(faces), F, _ptr(label), float(scale), float(cap), _ptr(area_q), _ptr(comp_faces),
+                   _ptr(comp_area), int(blocks), self.stream())
+        return area_q, comp_faces, comp_area
+
+    def mesh_sample(self, verts, faces, area_cum, a0, M, blocks=0):
+        """dmvs_mesh_sample_f32 (include/dmvs.h): M samples, one per a0 units of the running area sums area_cum [F] int64 (inclusive), at the
+        R2 sequence's coordinates inside their faces.  The caller keeps M a0 <= area_cum[-1].  -> (points [M,3] fp32, face_of [M] int32)"""
+        self._mesh_args("mesh_sample", verts, faces)
+        self._chk_typed("mesh_sample", (area_cum, torch.int64))
+        N, F, M = int(verts.shape[0]), int(faces.shape[0]), int(M)
+        if tuple(area_cum.shape) != (F,):
+            raise _lib.DmvsError(f"mesh_sample: area_cum must be [F] = [{F}], got {tuple(area_cum.shape)}")
+        if not 0 <= M <= 2 ** 31 - 1 or not 1 <= int(a0) < 2 ** 63:
+            raise _lib.DmvsError(f"mesh_sample: M = {M} and a0 = {a0}; 0 <= M < 2^31 and 1 <= a0 < 2^63")
+        if M > 0 and (N == 0 or F == 0):
+            raise _lib.DmvsError(f"mesh_sample: {M} samples of a mesh with {N} vertices and {F} faces")
+        points = torch.empty((M, 3), dtype=torch.float32, device=self.device)
+        face_of = torch.empty((M,), dtype=torch.int32, device=self.device)
+        self._call("dmvs_mesh_sample_f32", _ptr(verts), N, _ptr(faces), F, _ptr(area_cum), int(a0), M, _ptr(points), _ptr(face_of), int(blocks), self.stream())
+        return points, face_of
+
 
 class TsdfVolume:
     """The caller-owned state of dmvs_tsdf_integrate_f32 (include/dmvs.h), made zeroed by Ops.tsdf_volume: dims (nx, ny, nz), origin (HOST,

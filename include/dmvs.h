@@ -854,6 +854,53 @@ int dmvs_mesh_raster_resolve_f32(const uint64_t* zid, const float* verts, int64_
                                  const double* views, int64_t V, int32_t H, int32_t W, const uint8_t* vrgb, float* depth, int32_t* face,
                                  float* normal, uint8_t* rgb, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Cleaning and scoring an extracted mesh (added under ABI 4, additive; diffmvs_amd/mesh_clean.py, diffmvs_amd/mesh_eval.py): connected
+ * components, per-component face counts and areas, and points spread evenly by area.  Integer min, integer adds and fp64 in a fixed
+ * order: every output is bitwise independent of blocks, of timing and of the run.
+ *
+ * verts [N,3] fp32, faces [F,3] int32 (device).  blocks: workgroups of the grid-stride launches, 0 = the library's choice.
+ *
+ * dmvs_mesh_label_round_i32: ONE round of labelling; two vertices are connected when a face names both.  label [N] int32 is the caller's,
+ * filled with label[v] = v before the first round; state [2] int32 (device) is zeroed here on the stream.
+ *   hook (first launch): a face with an index outside [0, N) is skipped and counted in state[1].  For every other face
+ *     m = min over its vertices y of label[label[y]];  then for each of its vertices x, label[label[x]] and label[x] are lowered to m.
+ *   shortcut (second launch): every label[v] is lowered to label[label[v]].
+ *   "lowered": a u32 atomic-min behind a plain load, issued only when the loaded value is larger; every issued one adds 1 to state[0].
+ *   Labels only fall, every value written is a vertex of the same component, and a stale load can only be too high: it costs a spurious
+ *   count or one more round.  No launch relies on seeing another workgroup's writes of the same launch; nothing waits.  A round that
+ *   leaves state[0] == 0 wrote nothing, so all it read was settled at a launch boundary: every face's labels are equal and
+ *   label[label[v]] == label[v], hence label[v] is the SMALLEST VERTEX INDEX of v's component (v itself for a vertex no face names).
+ *   That fixpoint is unique; the number of rounds to it is not part of the contract.  state[0] and state[1] are exact while a
+ *   workgroup counts fewer than 2^31 / (workgroups of the round); beyond that they saturate (positive, below 2^31).
+ *   A label outside [0, N) (never with labels made here) is not followed.
+ *
+ * dmvs_mesh_face_tally_i64: area_q [F] int64; comp_faces [N] int32 and comp_area [N] int64 are zeroed here.  Per face, its vertices
+ * p0, p1, p2 widened to fp64, IEEE fp64 in exactly this order, no contraction:
+ *   a = p1 - p0,  b = p2 - p0,  c = (ay bz - az by, az bx - ax bz, ax by - ay bx),  area = 0.5 * sqrt((cx^2 + cy^2) + cz^2)
+ *   q = llrint(fmin(area * scale, cap)), or 0 where area is not finite;  area_q[f] = q
+ *   A face with an index outside [0, N) gets area_q = 0 and is counted nowhere.  Every other face adds 1 to comp_faces[r] and q to
+ *   comp_area[r], r = label[faces[f][0]] (a label outside [0, N): as an out-of-range face).  Integer atomics; a wave whose live lanes
+ *   share one root adds them up first (shuffles, registers, then LDS per workgroup), so the order of the sums is free.  scale: a positive finite power of two; 0 <= cap < 2^62; the
+ *   caller keeps F * cap < 2^62.
+ *
+ * dmvs_mesh_sample_f32: systematic sampling by area, one lane per sample k = 0 .. M - 1.  area_cum [F] int64: the caller's INCLUSIVE
+ * running sum of area_q; the caller keeps M * a0 <= area_cum[F - 1].
+ *   t = k * a0 + (a0 >> 1);  f = the smallest index with area_cum[f] > t (binary search; a face of zero area is never chosen)
+ *   r1 = (double)(uint32)((uint32)k * 3242174889u) * 2^-32,  r2 = (double)(uint32)((uint32)k * 2447445414u) * 2^-32  (the R2 sequence)
+ *   if r1 + r2 > 1.0:  r1 = 1 - r1,  r2 = 1 - r2
+ *   per coordinate, a = p1 - p0, b = p2 - p0 in fp64:  points[k] = (float)((p0 + r1 * a) + r2 * b);  face_of[k] = f
+ *   No such f, or a face with an index outside [0, N) (never with an area_cum made as above): points[k] = 0, face_of[k] = -1.
+ *
+ * F = 0 or N = 0 (and M = 0): nothing but the zeroed counters is touched.  DMVS_EINVAL (before any launch): a negative size, N or
+ * F >= 2^31, NULL operands with work to do (state always), an int32 / fp32 array not 4-byte or an int64 array not 8-byte aligned,
+ * blocks < 0, a scale that is not a positive finite power of two, cap not in [0, 2^62), a0 < 1, M < 0, M > 2^31 - 1, M a0 >= 2^63. */
+int dmvs_mesh_label_round_i32(const int32_t* faces, int64_t F, int64_t N, int32_t* label, int32_t* state, int32_t blocks, void* stream);
+int dmvs_mesh_face_tally_i64(const float* verts, int64_t N, const int32_t* faces, int64_t F, const int32_t* label, double scale, double cap,
+                             int64_t* area_q, int32_t* comp_faces, int64_t* comp_area, int32_t blocks, void* stream);
+int dmvs_mesh_sample_f32(const float* verts, int64_t N, const int32_t* faces, int64_t F, const int64_t* area_cum, int64_t a0, int64_t M,
+                         float* points, int32_t* face_of, int32_t blocks, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
