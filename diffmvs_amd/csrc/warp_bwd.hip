@@ -16,26 +16,19 @@
 // 4 bytes out of every 16 of the texel -- LPP lanes spread over the whole 4C-byte texel, CPL times over.  Round 6 (CS = LPP, "interleaved"):
 // lane `sub` owns channels sub, sub + LPP, ...: one atomic instruction covers LPP CONTIGUOUS floats of the texel (64 bytes at 16 lanes per
 // pixel), i.e. the L2's atomic units see C*4/64 full 64-byte requests per (pixel, tap) instead of CPL * C*4/64 quarter-filled ones.
-#include "dmvs_common.h"
+#include "warp_bwd_common.h"
 
 namespace {
-
-struct RayB {
-    float rx, ry, rz, tx, ty, tz;
-    __device__ __forceinline__ void init(const float* m, float x, float y) {
-        rx = m[0] * x + m[1] * y + m[2];
-        ry = m[3] * x + m[4] * y + m[5];
-        rz = m[6] * x + m[7] * y + m[8];
-        tx = m[9]; ty = m[10]; tz = m[11];
-    }
-};
 
 struct SampB {
     int x0, y0;
     float w[4];      // tap weights (00, 01, 10, 11), zero for taps outside the image / non-finite projections
 };
 
-__device__ __forceinline__ SampB project_b(const RayB& r, float depth, int Hs, int Ws) {
+// Kept apart from project_uv / make_samp (warp_tile.h) on purpose: this one divides (px / pz) where project_uv multiplies by
+// a Newton-refined reciprocal, and it selects the tap weights where make_samp folds the padding into the 1-D weights.  The
+// window pre-pass and the fp64 replicas in tests/test_ops.py pin project_uv's rules; one function for both would change bits.
+__device__ __forceinline__ SampB project_b(const Ray& r, float depth, int Hs, int Ws) {
     const float px = r.rx * depth + r.tx, py = r.ry * depth + r.ty;
     float pz = r.rz * depth + r.tz;
     if (pz == 0.0f) pz += 1e-8f;
@@ -115,12 +108,23 @@ __device__ __forceinline__ void bwd_sample(const float* view, float* gview, cons
 }
 
 // lane `sub` of a pixel's LPP lanes: float offset of its channel 0 inside a texel, stride between its channels, and channel j's index
-template <int C, int CPL, bool IL>
+template <int C_, int CPL_, bool IL_>
 struct LaneCh {
-    static constexpr int LPP = C / CPL, CS = IL ? LPP : 1;
+    static constexpr int C = C_, CPL = CPL_, LPP = C / CPL, CS = IL_ ? LPP : 1;
+    static constexpr bool IL = IL_;
     static __device__ __forceinline__ int base(int sub) { return IL ? sub : sub * CPL; }
     static __device__ __forceinline__ int ch(int sub, int j) { return base(sub) + j * CS; }
 };
+
+// The channels-per-lane table of the per-pixel kernels: calls f(LaneCh<C, CPL, IL>{}) for a supported (C, interleaved).
+// Interleaved: 16 lanes per pixel, lane = channel mod 16 (64-byte atomic requests).
+template <class F>
+int with_lane_ch(int C, bool il, F&& f) {
+    if (C == 48) return il ? f(LaneCh<48, 3, true>{}) : f(LaneCh<48, 3, false>{});
+    if (C == 32) return il ? f(LaneCh<32, 2, true>{}) : f(LaneCh<32, 4, false>{});
+    if (C == 16) return il ? f(LaneCh<16, 1, true>{}) : f(LaneCh<16, 4, false>{});
+    return DMVS_EINVAL;
+}
 
 // ------------------------------------------------------------------------------------------
 // backward of dmvs_warp_corr_init_f32.   gcor [B,S,G,D,H,W] -> gref [B,H,W,C] (written), gsrc [S,B,Hs,Ws,C] (+=)
@@ -149,7 +153,7 @@ warp_corr_init_bwd_kernel(const float* __restrict__ ref, const float* __restrict
     }
     const float dmin = disp_min[b], dmax = disp_max[b], dm1 = (float)(D - 1);
     for (int s = 0; s < S; ++s) {
-        RayB ray;
+        Ray ray;
         ray.init(rt + ((long)b * S + s) * 12, (float)x, (float)y);
         const long voff = ((long)s * B + b) * (long)Hs * Ws * C + L::base(sub);
         const float* view = src + voff;
@@ -211,6 +215,8 @@ __global__ void __launch_bounds__(DMVS_BLOCK) getcost_bwd_kernel(const dmvs_getc
         b = (int)(pix0 / hw);
     }
     const long yx = (long)y * W + x, pix = (long)b * hw + yx;
+    // tile_pixel's interval (warp_tile.h), spelled out: as a call of a shared helper, in any form tried, the flat interleaved
+    // kernels come out 2 VGPRs larger and <32, 2, 6> drops from 3 waves per SIMD to 2
     const float cur_inv = d.inv_depth[pix];
     float radius = (float)(N / 2) * d.interval;
     if (d.confidence) {
@@ -221,11 +227,7 @@ __global__ void __launch_bounds__(DMVS_BLOCK) getcost_bwd_kernel(const dmvs_getc
     const float dmin = d.disp_min[b], dmax = d.disp_max[b];
     float depth[N];
 #pragma unroll
-    for (int k = 0; k < N; ++k) {
-        float sk = (float)k * step;
-        sk += lo;
-        depth[k] = dmvs_disp_to_depth(fminf(fmaxf(sk, 0.0f), 1.0f), dmin, dmax);
-    }
+    for (int k = 0; k < N; ++k) depth[k] = hyp_depth(k, lo, step, dmin, dmax);
     const float inv_cg = 1.0f / (float)(C / G);
     float refv[CPL], gr[CPL];
 #pragma unroll
@@ -248,7 +250,7 @@ __global__ void __launch_bounds__(DMVS_BLOCK) getcost_bwd_kernel(const dmvs_getc
     }
     for (int s = 0; s < d.S; ++s) {
         const float w = d.view_w[((long)b * d.S + s) * Hv * Wv + vwi];
-        RayB ray;
+        Ray ray;
         ray.init(d.rt + ((long)b * d.S + s) * 12, (float)x, (float)y);
         const long voff = ((long)s * d.B + b) * hw * C + L::base(sub);
         Scatter<CPL, CS> sc;
@@ -282,46 +284,31 @@ extern "C" int dmvs_warp_corr_init_bwd_f32(const float* ref, const float* src, c
     if (!gather && C == 48 && D <= 256)        // the model's stage 1: LDS windows (warp_init_bwd_win.hip)
         return dmvs_warp_init_bwd_win_dispatch(ref, src, rt, disp_min, disp_max, gcor, gref, gsrc, B, S, C, D, H, W, Hs, Ws, st);
     const long npix = (long)B * H * W;
-    dim3 block(DMVS_BLOCK);
-#define DMVS_WIB_BWD(CC, CPLL, ILL)                                                                                                       \
-    hipLaunchKernelGGL((warp_corr_init_bwd_kernel<CC, CPLL, ILL>), dim3(dmvs_ceil_div(npix, DMVS_BLOCK / (CC / CPLL))), block, 0, st, ref, src, \
-                       rt, disp_min, disp_max, gcor, gref, gsrc, B, S, D, H, W, Hs, Ws)
-    if (gather == DMVS_BWD_GATHER_INTERLEAVED) {      // 16 lanes per pixel, lane = channel mod 16: 64-byte atomic requests
-        if (C == 48) DMVS_WIB_BWD(48, 3, true);
-        else if (C == 32) DMVS_WIB_BWD(32, 2, true);
-        else if (C == 16) DMVS_WIB_BWD(16, 1, true);
-        else return DMVS_EINVAL;
-    } else if (C == 48) {
-        DMVS_WIB_BWD(48, 3, false);
-    } else if (C == 32) {
-        DMVS_WIB_BWD(32, 4, false);
-    } else if (C == 16) {
-        DMVS_WIB_BWD(16, 4, false);
-    } else {
-        return DMVS_EINVAL;
-    }
-#undef DMVS_WIB_BWD
-    return dmvs_launch_status();
+    return with_lane_ch(C, gather == DMVS_BWD_GATHER_INTERLEAVED, [&](auto l) {
+        using L = decltype(l);
+        hipLaunchKernelGGL((warp_corr_init_bwd_kernel<L::C, L::CPL, L::IL>), dim3(dmvs_ceil_div(npix, DMVS_BLOCK / L::LPP)),
+                           dim3(DMVS_BLOCK), 0, st, ref, src, rt, disp_min, disp_max, gcor, gref, gsrc, B, S, D, H, W, Hs, Ws);
+        return dmvs_launch_status();
+    });
 }
 
-template <int C, int CPL, bool IL>
+// TILED: one launch over the 16x16 tiles of the pre-pass's list (d.worklist); else over every pixel
+template <bool TILED>
 static int launch_getcost_bwd(const dmvs_getcost_desc& d, const float* gcost, float* gref, float* gsrc, hipStream_t st) {
-    dim3 grid(dmvs_ceil_div((long)d.B * d.H * d.W, DMVS_BLOCK / (C / CPL))), block(DMVS_BLOCK);
-    if (d.n == 4) hipLaunchKernelGGL((getcost_bwd_kernel<C, CPL, 4, false, IL>), grid, block, 0, st, d, gcost, gref, gsrc);
-    else if (d.n == 6) hipLaunchKernelGGL((getcost_bwd_kernel<C, CPL, 6, false, IL>), grid, block, 0, st, d, gcost, gref, gsrc);
-    else return DMVS_EINVAL;
-    return dmvs_launch_status();
-}
-
-template <int C, int CPL, bool IL>
-static int launch_getcost_bwd_tiles(const dmvs_getcost_desc& d, const float* gcost, float* gref, float* gsrc, hipStream_t st) {
-    constexpr int PPB = DMVS_BLOCK / (C / CPL), T = DMVS_GETCOST_TILE, BPT = T * T / PPB;
-    const long tiles = (long)d.B * ((d.H + T - 1) / T) * ((d.W + T - 1) / T);
-    dim3 grid((unsigned)(tiles * BPT)), block(DMVS_BLOCK);
-    if (d.n == 4) hipLaunchKernelGGL((getcost_bwd_kernel<C, CPL, 4, true, IL>), grid, block, 0, st, d, gcost, gref, gsrc);
-    else if (d.n == 6) hipLaunchKernelGGL((getcost_bwd_kernel<C, CPL, 6, true, IL>), grid, block, 0, st, d, gcost, gref, gsrc);
-    else return DMVS_EINVAL;
-    return dmvs_launch_status();
+    return with_lane_ch(d.C, (d.tune & DMVS_TUNE_BWD_INTERLEAVED) != 0, [&](auto l) {
+        using L = decltype(l);
+        if constexpr (TILED && L::C == 48) {
+            return DMVS_EINVAL;         // no window kernel for C = 48, so no tiled per-pixel kernel either
+        } else {
+            constexpr int PPB = DMVS_BLOCK / L::LPP, T = DMVS_GETCOST_TILE, BPT = T * T / PPB;
+            const long tiles = (long)d.B * ((d.H + T - 1) / T) * ((d.W + T - 1) / T);
+            dim3 grid(TILED ? (unsigned)(tiles * BPT) : dmvs_ceil_div((long)d.B * d.H * d.W, PPB)), block(DMVS_BLOCK);
+            if (d.n == 4) hipLaunchKernelGGL((getcost_bwd_kernel<L::C, L::CPL, 4, TILED, L::IL>), grid, block, 0, st, d, gcost, gref, gsrc);
+            else if (d.n == 6) hipLaunchKernelGGL((getcost_bwd_kernel<L::C, L::CPL, 6, TILED, L::IL>), grid, block, 0, st, d, gcost, gref, gsrc);
+            else return DMVS_EINVAL;
+            return dmvs_launch_status();
+        }
+    });
 }
 
 int dmvs_getcost_bwd_win_dispatch(const dmvs_getcost_desc& d, const float* gcost, float* gref, float* gsrc, hipStream_t st);
@@ -331,25 +318,13 @@ extern "C" int dmvs_getcost_bwd_f32(const dmvs_getcost_desc* dp, const float* gc
     dmvs_getcost_desc d = *dp;
     if (d.G != 4 || !d.ref || !d.src || !d.rt || !d.inv_depth || !d.view_w || (d.n != 4 && d.n != 6)) return DMVS_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    const bool il = (d.tune & DMVS_TUNE_BWD_INTERLEAVED) != 0;
     if (d.worklist && (d.C == 32 || d.C == 16) && d.S <= DMVS_GETCOST_MAX_WINDOW_VIEWS) {
         // LDS-window tiles first, then one launch for the rest: the listed tiles, or (pre-pass: mostly misfits) every pixel
         if (int rc = dmvs_getcost_bwd_win_dispatch(d, gcost, gref, gsrc, st)) return rc;
-        if (il) return d.C == 32 ? launch_getcost_bwd_tiles<32, 2, true>(d, gcost, gref, gsrc, st) : launch_getcost_bwd_tiles<16, 1, true>(d, gcost, gref, gsrc, st);
-        return d.C == 32 ? launch_getcost_bwd_tiles<32, 4, false>(d, gcost, gref, gsrc, st)
-                         : launch_getcost_bwd_tiles<16, 4, false>(d, gcost, gref, gsrc, st);
+        return launch_getcost_bwd<true>(d, gcost, gref, gsrc, st);
     }
     d.worklist = nullptr;
-    if (il) {
-        if (d.C == 48) return launch_getcost_bwd<48, 3, true>(d, gcost, gref, gsrc, st);
-        if (d.C == 32) return launch_getcost_bwd<32, 2, true>(d, gcost, gref, gsrc, st);
-        if (d.C == 16) return launch_getcost_bwd<16, 1, true>(d, gcost, gref, gsrc, st);
-        return DMVS_EINVAL;
-    }
-    if (d.C == 48) return launch_getcost_bwd<48, 3, false>(d, gcost, gref, gsrc, st);
-    if (d.C == 32) return launch_getcost_bwd<32, 4, false>(d, gcost, gref, gsrc, st);
-    if (d.C == 16) return launch_getcost_bwd<16, 4, false>(d, gcost, gref, gsrc, st);
-    return DMVS_EINVAL;
+    return launch_getcost_bwd<false>(d, gcost, gref, gsrc, st);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -16,16 +16,14 @@ template <int C, int N>
 __global__ void __launch_bounds__(DMVS_BLOCK, 2)
 getcost_bwd_win_kernel(const dmvs_getcost_desc d, const float* __restrict__ gcost, float* __restrict__ gref,
                        float* __restrict__ gsrc, int tiles_x, int tiles_y) {
-    constexpr int G = 4, NCH = C / 4, CPG = NCH / 4, TS = C + 4;
-    constexpr int WH = WinCfg<C>::WH;
-    constexpr int SLOTS = WW * (NCH + 1), SUBS = (SLOTS + 63) / 64;
-    __shared__ __attribute__((aligned(16))) float win[WW * WH * TS];
+    constexpr int G = 4, NCH = C / 4, CPG = NCH / 4;
+    __shared__ __attribute__((aligned(16))) float win[WW * WinCfg<C>::WH * WinLane<NCH>::TS];
     __shared__ int sbox[MAXS][4];
 
     if (d.worklist[1]) return;           // pre-pass: the per-pixel kernel takes every tile
     const int tile = (int)dmvs_xcd_contiguous_block(blockIdx.x, gridDim.x);
     if (ws_flags(d.worklist)[tile]) return;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int H = d.H, W = d.W;
     const long hw = (long)H * W;
     int b, xc, yc;
@@ -56,148 +54,57 @@ getcost_bwd_win_kernel(const dmvs_getcost_desc d, const float* __restrict__ gcos
 #pragma unroll
         for (int k = 0; k < N; ++k) gk[k][g] = live ? gcost[((long)b * G * N + g * N + k) * hw + yx] / wsum : 0.0f;
 
-    int dcol[SUBS], dch[SUBS];
-#pragma unroll
-    for (int i = 0; i < SUBS; ++i) {
-        const int slot = i * 64 + lane;
-        dcol[i] = slot / (NCH + 1);
-        dch[i] = slot < SLOTS ? slot - dcol[i] * (NCH + 1) : NCH;
-    }
+    WinLane<NCH> ln;
+    ln.init();
 
     for (int s = 0; s < d.S; ++s) {
         const float w = vwp[(long)s * Hv * Wv];
-        RayW ray;
+        Ray ray;
         ray.init(d.rt + ((long)b * d.S + s) * 12, (float)xc, (float)yc);
         const long voff = ((long)s * d.B + b) * hw * C;
-        const float* view = d.src + voff;
-        float* gview = gsrc + voff;
         __syncthreads();        // boxes published (s = 0) / the previous view's flush is done with the window
-        const int bx0 = sbox[s][0], by0 = sbox[s][1], ncols = sbox[s][2], nrows = sbox[s][3];
-        if (ncols <= 0) continue;           // every tap of the tile is padding in this view (workgroup-uniform)
-        for (int r = wave; r < nrows; r += DMVS_BLOCK / 64) {
-            const float* rowp = view + ((long)(by0 + r) * W + bx0) * C;
-#pragma unroll
-            for (int i = 0; i < SUBS; ++i) {
-                if (dch[i] < NCH && dcol[i] < ncols) {
-                    const float* srcp = rowp + dcol[i] * C + dch[i] * 4;
-                    float* dstp = win + (r * SLOTS + i * 64) * 4;
-                    __builtin_amdgcn_global_load_lds(srcp, DMVS_LDS_PTR(dstp), 16, 0, 0);
-                }
-            }
-        }
+        const WinBox bx = {sbox[s][0], sbox[s][1], sbox[s][2], sbox[s][3]};
+        if (bx.ncols <= 0) continue;        // every tap of the tile is padding in this view (workgroup-uniform)
+        win_stage<NCH, C>(win, ln, bx, d.src + voff, W);
         DMVS_DMA_BARRIER();        // source window resident
 
-        // both passes walk the hypotheses once and act per distinct footprint with the accumulated tap weights.
-        // A rolled loop with ONE emit site (the emit bodies are 4*C LDS reads / atomics): hypothesis k's depth and
-        // gradients are picked by select chains on the wave-uniform k; iteration N only flushes the last footprint.
-        auto walk = [&](auto&& emit) {
-            int fx = 0, fy = 0;
-            bool open = false;
-            float Wt[4][G];
+        // both passes walk the hypotheses once; hypothesis k's depth and gradients are picked by select chains on the
+        // wave-uniform k (walk_footprints keeps the loop rolled).  One sampler handed to walk_footprints twice, the view
+        // weight as its scale: behind a wrapper lambda, or scaled in here, the C = 32 kernels spill 100-300 bytes more
+        auto sample = [&](int k, SampW& sp, float (&gkk)[G]) {
+            float dk = depth[0];
 #pragma unroll
-            for (int t = 0; t < 4; ++t)
+            for (int g = 0; g < G; ++g) gkk[g] = gk[0][g];
 #pragma unroll
-                for (int g = 0; g < G; ++g) Wt[t][g] = 0.0f;
-#pragma unroll 1
-            for (int k = 0; k <= N; ++k) {
-                float dk = depth[0], gkk[G];
+            for (int kk = 1; kk < N; ++kk) {
+                dk = k == kk ? depth[kk] : dk;
 #pragma unroll
-                for (int g = 0; g < G; ++g) gkk[g] = gk[0][g];
-#pragma unroll
-                for (int kk = 1; kk < N; ++kk) {
-                    dk = k == kk ? depth[kk] : dk;
-#pragma unroll
-                    for (int g = 0; g < G; ++g) gkk[g] = k == kk ? gk[kk][g] : gkk[g];
-                }
-                float u, v, z;
-                bool fin;
-                project_uv(ray, dk, u, v, z, fin);
-                const SampW sp = make_samp(u, v, fin, H, W);
-                const bool change = k == N || !open || sp.x0 != fx || sp.y0 != fy;
-                if (open && change) emit(fx, fy, Wt);
-                if (k == N) break;
-                if (change) {
-                    open = true;
-                    fx = sp.x0;
-                    fy = sp.y0;
-#pragma unroll
-                    for (int t = 0; t < 4; ++t)
-#pragma unroll
-                        for (int g = 0; g < G; ++g) Wt[t][g] = 0.0f;
-                }
-#pragma unroll
-                for (int g = 0; g < G; ++g) {
-                    const float gc = gkk[g] * w;
-                    Wt[0][g] = fmaf(gc, sp.w00, Wt[0][g]);
-                    Wt[1][g] = fmaf(gc, sp.w01, Wt[1][g]);
-                    Wt[2][g] = fmaf(gc, sp.w10, Wt[2][g]);
-                    Wt[3][g] = fmaf(gc, sp.w11, Wt[3][g]);
-                }
+                for (int g = 0; g < G; ++g) gkk[g] = k == kk ? gk[kk][g] : gkk[g];
             }
-        };
-        auto tap_offsets = [&](int fx, int fy, int (&off)[4]) {
-            const int xa = min(max(fx - bx0, 0), ncols - 1), xb = min(max(fx + 1 - bx0, 0), ncols - 1);
-            const int ya = min(max(fy - by0, 0), nrows - 1), yb = min(max(fy + 1 - by0, 0), nrows - 1);
-            const int ra = __mul24(ya, WW * TS), rb = __mul24(yb, WW * TS), ca = __mul24(xa, TS), cb = __mul24(xb, TS);
-            off[0] = ra + ca; off[1] = ra + cb; off[2] = rb + ca; off[3] = rb + cb;
+            float u, v, z;
+            bool fin;
+            project_uv(ray, dk, u, v, z, fin);
+            sp = make_samp(u, v, fin, H, W);
         };
 
         // ---- pass A: grad_ref from the source window
-        walk([&](int fx, int fy, const float (&Wt)[4][G]) {
+        walk_footprints<G>(0, N, w, sample, [&](int fx, int fy, const float (&Wt)[4][G]) {
             int off[4];
-            tap_offsets(fx, fy, off);
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-                for (int j = 0; j < NCH; ++j) {
-                    const float4 q = *reinterpret_cast<const float4*>(win + off[t] + 4 * j);
-                    const float wt = Wt[t][j / CPG];
-                    gr[4 * j] = fmaf(wt, q.x, gr[4 * j]);
-                    gr[4 * j + 1] = fmaf(wt, q.y, gr[4 * j + 1]);
-                    gr[4 * j + 2] = fmaf(wt, q.z, gr[4 * j + 2]);
-                    gr[4 * j + 3] = fmaf(wt, q.w, gr[4 * j + 3]);
-                }
+            win_tap_offsets<NCH>(fx, fy, bx, off);
+            win_gather<NCH, CPG, G>(win, off, Wt, gr);
         });
         __syncthreads();        // every lane is done with the source window
-        for (int e = tid * 4; e < nrows * (WW * TS); e += DMVS_BLOCK * 4)
-            *reinterpret_cast<float4*>(win + e) = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        win_zero<NCH>(win, bx.nrows);
         __syncthreads();
 
-        // ---- pass B: scatter into the gradient window (LDS atomics: neighbouring pixels share texels)
-        walk([&](int fx, int fy, const float (&Wt)[4][G]) {
+        // ---- pass B: the window becomes the gradient tile, then goes to grad_src
+        walk_footprints<G>(0, N, w, sample, [&](int fx, int fy, const float (&Wt)[4][G]) {
             int off[4];
-            tap_offsets(fx, fy, off);
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                if (Wt[t][0] == 0.0f && Wt[t][1] == 0.0f && Wt[t][2] == 0.0f && Wt[t][3] == 0.0f) continue;   // padding tap
-#pragma unroll
-                for (int j = 0; j < NCH; ++j) {
-                    const float4 q = refp4[j];
-                    const float wt = Wt[t][j / CPG] * inv_cg;
-                    atomicAdd(win + off[t] + 4 * j, wt * q.x);
-                    atomicAdd(win + off[t] + 4 * j + 1, wt * q.y);
-                    atomicAdd(win + off[t] + 4 * j + 2, wt * q.z);
-                    atomicAdd(win + off[t] + 4 * j + 3, wt * q.w);
-                }
-            }
+            win_tap_offsets<NCH>(fx, fy, bx, off);
+            win_scatter<NCH, CPG, G>(win, off, Wt, refp4, inv_cg);
         });
         __syncthreads();
-
-        // ---- flush: one global atomic per window texel-channel, rows contiguous in grad_src
-        for (int r = wave; r < nrows; r += DMVS_BLOCK / 64) {
-            float* growp = gview + ((long)(by0 + r) * W + bx0) * C;
-#pragma unroll
-            for (int i = 0; i < SUBS; ++i) {
-                if (dch[i] < NCH && dcol[i] < ncols) {
-                    const float4 q = *reinterpret_cast<const float4*>(win + (r * SLOTS + i * 64 + lane) * 4);
-                    float* gp = growp + dcol[i] * C + dch[i] * 4;
-                    if (q.x != 0.0f) atomicAdd(gp, q.x);
-                    if (q.y != 0.0f) atomicAdd(gp + 1, q.y);
-                    if (q.z != 0.0f) atomicAdd(gp + 2, q.z);
-                    if (q.w != 0.0f) atomicAdd(gp + 3, q.w);
-                }
-            }
-        }
+        win_flush<NCH, C>(win, ln, bx, gsrc + voff, W);
     }
     if (live) {
         float4* gp = reinterpret_cast<float4*>(gref + pc * C);

@@ -1347,7 +1347,7 @@ def _sweep_depth32(disp_min, disp_max, D):
 
 
 def _getcost_depth32(inv, conf, n, interval, rmin, rmax, disp_min, disp_max):
-    """GetCost's n depths per pixel, fp32, in the op order of tile_pixel / hyp_depth (csrc/warp_tile.h) -> [B,n,H,W]"""
+    """GetCost's n depths per pixel, fp32, in the op order of tile_pixel (csrc/warp_tile.h) / hyp_depth (csrc/warp_bwd_common.h) -> [B,n,H,W]"""
     f = lambda v: torch.tensor(v, dtype=torch.float32)
     cur = inv.squeeze(1)
     radius = f(float(n // 2)) * f(interval)
