@@ -117,7 +117,12 @@ SIGNATURES = {
     "dmvs_mesh_label_round_i32": [_P, C.c_int64, C.c_int64, _P, _P, _I, _P],
     "dmvs_mesh_face_tally_i64": [_P, C.c_int64, _P, C.c_int64, _P, C.c_double, C.c_double, _P, _P, _P, _I, _P],
     "dmvs_mesh_sample_f32": [_P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int64, _P, _P, _I, _P],
+    "dmvs_mesh_cluster_verts_i64": [_P, _P, C.c_int64, _P, C.c_int64, _P, C.c_double, _P, _P, _P, _I, _P],
+    "dmvs_mesh_cluster_quadrics_i64": [_P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, C.c_double, C.c_double, C.c_double, _P, _P, _I, _P],
+    "dmvs_mesh_cluster_place_f32": [C.c_int64, _P, _P, _P, _P, _P, _P, C.c_double, C.c_double, C.c_double, _I, _P, _P, _P, _P],
+    "dmvs_mesh_cluster_remap_i32": [_P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, _P, _P, _P, _I, _P],
 }
+SIMPLIFY_QUADRIC, SIMPLIFY_MEAN = 0, 1      # dmvs.h: DMVS_SIMPLIFY_*
 VIEW_SELECT_MAX_IMAGES, VIEW_SELECT_MAX_LIST = 16384, 1 << 23      # dmvs.h: DMVS_VIEW_SELECT_MAX_IMAGES, DMVS_VIEW_SELECT_MAX_LIST
 CLOUD_MAX_RINGS, CLOUD_MAX_KEY_BITS, CLOUD_MAX_THRESHOLDS = 1024, 62, 16      # dmvs.h: DMVS_CLOUD_MAX_*
 CLOUD_MOMENTS, CLOUD_MAX_POLYGON = 20, 256      # dmvs.h: DMVS_CLOUD_MOMENTS, DMVS_CLOUD_MAX_POLYGON

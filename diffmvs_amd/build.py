@@ -18,7 +18,7 @@ CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libdmvs_hip.so")
 PROBE_LIB = os.path.join(PKG, "libdmvs_probe.so")      # measurement probes (bench.py's untimed roofline legs); never loaded by the path
 PROBE_SOURCES = ["probe/getcost_probe.hip", "probe/random_line_gather.hip"]
-SOURCES = ["conv2d_k33.hip", "conv2d_k55.hip", "conv2d_k77.hip", "conv2d_k15.hip", "conv2d.hip", "stem.hip", "stem3.hip", "conv1_pair.hip", "fpn_tail.hip", "conv3d.hip", "warp_quad.hip", "warp_bwd.hip", "warp_bwd_win.hip", "warp_init_bwd_win.hip", "misc.hip", "mask_upsample.hip", "optim.hip", "norm.hip", "fusion.hip", "view_select.hip", "cloud_eval.hip", "cloud_register.hip", "depth_eval.hip", "cloud_render.hip", "depth_normals.hip", "tsdf.hip", "mesh_render.hip", "mesh_clean.hip"]
+SOURCES = ["conv2d_k33.hip", "conv2d_k55.hip", "conv2d_k77.hip", "conv2d_k15.hip", "conv2d.hip", "stem.hip", "stem3.hip", "conv1_pair.hip", "fpn_tail.hip", "conv3d.hip", "warp_quad.hip", "warp_bwd.hip", "warp_bwd_win.hip", "warp_init_bwd_win.hip", "misc.hip", "mask_upsample.hip", "optim.hip", "norm.hip", "fusion.hip", "view_select.hip", "cloud_eval.hip", "cloud_register.hip", "depth_eval.hip", "cloud_render.hip", "depth_normals.hip", "tsdf.hip", "mesh_render.hip", "mesh_clean.hip", "mesh_simplify.hip"]
 
 
 def _deps():

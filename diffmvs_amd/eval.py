@@ -142,6 +142,8 @@ def main(argv=None, device=None):
     ap.add_argument("--mesh_min_weight", type=int, default=2, help="--mesh: a voxel counts as observed from this many views on")
     ap.add_argument("--mesh_min_component", type=int, default=0, help="--mesh: drop connected components with fewer faces (floaters) before the mesh is written "
                     "(diffmvs_amd.mesh_clean); mesh[scene] gains `cleaned`")
+    ap.add_argument("--mesh_simplify", type=float, default=None, metavar="V", help="--mesh: cluster the mesh on a lattice of cells V voxels wide before it is "
+                    "written, after --mesh_min_component (diffmvs_amd.mesh_simplify); mesh[scene] gains `simplified`")
     ap.add_argument("--mesh_score", type=float, default=None, metavar="SPACING", help="--mesh with --gt_ply: also score the mesh, sampled at one point per SPACING^2 of "
                     "area, with the cloud's transform, crop, max distance and thresholds (diffmvs_amd.mesh_eval); adds mesh_eval[scene] to the result")
     ap.add_argument("--gt_ply", default=None, help="with --filter: score every fused cloud against this ground-truth PLY ('{scene}' is substituted) "
@@ -214,7 +216,8 @@ def main(argv=None, device=None):
                 from . import mesh
                 res.setdefault("mesh", {})[scene] = mesh.mesh_scene(
                     os.path.join(a.outdir, scene), os.path.join(a.testpath, scene), a.dataset, voxel=a.mesh_voxel, resolution=a.mesh_resolution,
-                    trunc=a.mesh_trunc, min_weight=a.mesh_min_weight, device=device, min_component_faces=a.mesh_min_component)
+                    trunc=a.mesh_trunc, min_weight=a.mesh_min_weight, device=device, min_component_faces=a.mesh_min_component,
+                    simplify_voxels=a.mesh_simplify)
             if a.gt_ply:
                 from . import cloud_eval, cloud_register
                 extra = {}

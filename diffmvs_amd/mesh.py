@@ -3,6 +3,7 @@ over its zero set (dmvs_tsdf_* of include/dmvs.h, csrc/tsdf.hip; Ops.tsdf_integr
 
     python -m diffmvs_amd.mesh --outdir <eval output> [--testpath <root> --dataset dtu --testlist list.txt]
         [--voxel S | --resolution N] [--trunc 4] [--min_weight 2] [--bounds x0 y0 z0 x1 y1 z1] [--out mesh.ply] [--min_component N]
+        [--simplify V]
 
 reads the tree diffmvs_amd.eval (--filter) leaves behind -- cams/, images/, depth_fused/ (fusion.filter_depth(write_fused=True): the
 depth averaged over the consistent views) or else depth_est/, and mask/*_final.png or else every finite positive depth -- and writes a
@@ -107,11 +108,13 @@ def scene_views(out_folder, pair_folder, dataset):
 
 def mesh_scene(out_folder, pair_folder=None, dataset="dtu", voxel=None, resolution=512, trunc=4.0, min_weight=2, bounds=None, out=None,
                device="cuda:0", ops: Ops | None = None, chunk=_lib.TSDF_VIEW_CHUNK, max_voxels=2 ** 29, stride=4, colour=True,
-               min_component_faces=0) -> dict:
+               min_component_faces=0, simplify_voxels=None) -> dict:
     """One scene's output tree -> <out_folder>/mesh.ply (or `out`).  The truncation distance is trunc voxels; bounds (x0 y0 z0 x1 y1 z1)
     default to auto_bounds widened by tau + h.  The views stream through the volume `chunk` at a time.
     min_component_faces > 0: connected components with fewer faces are dropped before the file is written (mesh_clean.clean).
-    -> {"ply", "vertices", "faces", "dims", "voxel", "observed_voxels" (Wt >= min_weight), "views", "bounds"[, "cleaned"]}"""
+    simplify_voxels: after that the mesh is clustered on a lattice of cells this many voxels wide, anchored at the volume's origin
+    (mesh_simplify.simplify).
+    -> {"ply", "vertices", "faces", "dims", "voxel", "observed_voxels" (Wt >= min_weight), "views", "bounds"[, "cleaned"][, "simplified"]}"""
     from PIL import Image
     ops = ops or Ops.for_device(device)
     dev = ops.device
@@ -162,6 +165,10 @@ def mesh_scene(out_folder, pair_folder=None, dataset="dtu", voxel=None, resoluti
     if int(min_component_faces) > 0:
         from . import mesh_clean
         verts, rgb, faces, cleaned = mesh_clean.clean(ops, verts, rgb, faces, min_faces=int(min_component_faces))
+    simplified = None
+    if simplify_voxels is not None:
+        from . import mesh_simplify
+        verts, rgb, faces, simplified = mesh_simplify.simplify(ops, verts, rgb, faces, float(simplify_voxels) * vol.h, origin=vol.origin)
     out = out or os.path.join(out_folder, "mesh.ply")
     if os.path.dirname(out):
         os.makedirs(os.path.dirname(out), exist_ok=True)
@@ -170,6 +177,8 @@ def mesh_scene(out_folder, pair_folder=None, dataset="dtu", voxel=None, resoluti
            "observed_voxels": int((vol.Wt >= int(min_weight)).sum()), "views": len(ids), "bounds": [float(x) for x in np.concatenate([lo, hi])]}
     if cleaned is not None:
         res["cleaned"] = cleaned
+    if simplified is not None:
+        res["simplified"] = simplified
     return res
 
 
@@ -186,6 +195,8 @@ def main(argv=None, device="cuda:0", ops=None):
     ap.add_argument("--bounds", type=float, nargs=6, default=None, metavar=("x0", "y0", "z0", "x1", "y1", "z1"))
     ap.add_argument("--out", default=None, help="the PLY to write (default: <outdir>/<scene>/mesh.ply)")
     ap.add_argument("--min_component", type=int, default=0, help="drop connected components with fewer faces (floaters) before writing")
+    ap.add_argument("--simplify", type=float, default=None, metavar="V", help="cluster the mesh on a lattice of cells V voxels wide before writing "
+                    "(diffmvs_amd.mesh_simplify; after --min_component)")
     a = ap.parse_args(argv)
     scenes = [""]
     if a.testlist:
@@ -197,7 +208,7 @@ def main(argv=None, device="cuda:0", ops=None):
     for scene in scenes:
         res[scene] = mesh_scene(os.path.join(a.outdir, scene), os.path.join(a.testpath, scene) if a.testpath else None, a.dataset, voxel=a.voxel,
                                 resolution=a.resolution, trunc=a.trunc, min_weight=a.min_weight, bounds=a.bounds, out=a.out, device=device, ops=ops,
-                                min_component_faces=a.min_component)
+                                min_component_faces=a.min_component, simplify_voxels=a.simplify)
     print(json.dumps({"mesh": res}), flush=True)
     return res
 

@@ -1247,6 +1247,76 @@ class Ops:
         self._call("dmvs_mesh_sample_f32", _ptr(verts), N, _ptr(faces), F, _ptr(area_cum), int(a0), M, _ptr(points), _ptr(face_of), int(blocks), self.stream())
         return points, face_of
 
+    # ------------------------------------------------------------------ simplifying a mesh (diffmvs_amd/mesh_simplify.py)
+    def _cluster_args(self, what, verts, faces, cluster, K, origin):
+        """the checks the clustering passes share -> (N, K, the HOST origin)"""
+        if faces is not None:
+            self._mesh_args(what, verts, faces)
+        self._chk_typed(what, (verts, torch.float32), (cluster, torch.int32))
+        N = int(verts.shape[0])
+        if verts.dim() != 2 or verts.shape[1] != 3 or tuple(cluster.shape) != (N,):
+            raise _lib.DmvsError(f"{what}: verts must be [N,3] and cluster [N], got {tuple(verts.shape)} and {tuple(cluster.shape)}")
+        if not 0 <= int(K) <= 2 ** 31 - 1:
+            raise _lib.DmvsError(f"{what}: {K} clusters; 0 .. 2^31 - 1 are supported")
+        return N, int(K), None if origin is None else (C.c_double * 3)(*[float(v) for v in origin])
+
+    def mesh_cluster_verts(self, verts, rgb, cluster, K, origin, cell, blocks=0):
+        """dmvs_mesh_cluster_verts_i64 (include/dmvs.h): cluster [N] int32 (outside [0, K): none); origin: three doubles; rgb [N,3] uint8 or
+        None.  -> (cnt [K] int32, pos_q [K,3] int64, rgb_sum [K,3] int64 or None)"""
+        N, K, o = self._cluster_args("mesh_cluster_verts", verts, None, cluster, K, origin)
+        self._chk_typed("mesh_cluster_verts", (rgb, torch.uint8))
+        if rgb is not None and tuple(rgb.shape) != (N, 3):
+            raise _lib.DmvsError(f"mesh_cluster_verts: rgb must be [N,3] = [{N},3], got {tuple(rgb.shape)}")
+        cnt = torch.empty((K,), dtype=torch.int32, device=self.device)
+        pos_q = torch.empty((K, 3), dtype=torch.int64, device=self.device)
+        rgb_sum = torch.empty((K, 3), dtype=torch.int64, device=self.device) if rgb is not None else None
+        self._call("dmvs_mesh_cluster_verts_i64", _ptr(verts), _ptr(rgb), N, _ptr(cluster), K, o, float(cell), _ptr(cnt), _ptr(pos_q), _ptr(rgb_sum),
+                   int(blocks), self.stream())
+        return cnt, pos_q, rgb_sum
+
+    def mesh_cluster_quadrics(self, verts, faces, cluster, K, origin, cell, scale, cap, blocks=0):
+        """dmvs_mesh_cluster_quadrics_i64 (include/dmvs.h): scale: a power of two; cap: the bound of one face's weight.
+        -> (quad_q [K,10] int64, state [2] int64 (device): bad faces, flat faces)"""
+        N, K, o = self._cluster_args("mesh_cluster_quadrics", verts, faces, cluster, K, origin)
+        quad_q = torch.empty((K, 10), dtype=torch.int64, device=self.device)
+        state = torch.empty((2,), dtype=torch.int64, device=self.device)
+        self._call("dmvs_mesh_cluster_quadrics_i64", _ptr(verts), N, _ptr(faces), int(faces.shape[0]), _ptr(cluster), K, o, float(cell), float(scale),
+                   float(cap), _ptr(quad_q), _ptr(state), int(blocks), self.stream())
+        return quad_q, state
+
+    def mesh_cluster_place(self, cnt, pos_q, rgb_sum, quad_q, cells, origin, cell, scale, reg, mean=False):
+        """dmvs_mesh_cluster_place_f32 (include/dmvs.h): the sums of the two passes above, cells [K,3] int64: the clusters' lattice cells;
+        mean: every cluster at the mean of its vertices.  -> (verts [K,3] fp32, rgb [K,3] uint8 or None, state [1] int64 (device): clusters
+        that have a quadric and fell back to the mean)"""
+        self._chk_typed("mesh_cluster_place", (cnt, torch.int32), (pos_q, torch.int64), (rgb_sum, torch.int64), (quad_q, torch.int64), (cells, torch.int64))
+        K = int(cnt.shape[0])
+        if tuple(cnt.shape) != (K,) or tuple(pos_q.shape) != (K, 3) or tuple(quad_q.shape) != (K, 10) or tuple(cells.shape) != (K, 3) or (
+                rgb_sum is not None and tuple(rgb_sum.shape) != (K, 3)):
+            raise _lib.DmvsError(f"mesh_cluster_place: cnt [K], pos_q [K,3], rgb_sum [K,3], quad_q [K,10] and cells [K,3] with K = {K} are expected")
+        out = torch.empty((K, 3), dtype=torch.float32, device=self.device)
+        out_rgb = torch.empty((K, 3), dtype=torch.uint8, device=self.device) if rgb_sum is not None else None
+        state = torch.empty((1,), dtype=torch.int64, device=self.device)
+        self._call("dmvs_mesh_cluster_place_f32", K, _ptr(cnt), _ptr(pos_q), _ptr(rgb_sum), _ptr(quad_q), _ptr(cells),
+                   (C.c_double * 3)(*[float(v) for v in origin]), float(cell), float(scale), float(reg),
+                   _lib.SIMPLIFY_MEAN if mean else _lib.SIMPLIFY_QUADRIC, _ptr(out), _ptr(out_rgb), _ptr(state), self.stream())
+        return out, out_rgb, state
+
+    def mesh_cluster_remap(self, verts, faces, cluster, K, new_verts=None, blocks=0):
+        """dmvs_mesh_cluster_remap_i32 (include/dmvs.h): new_verts [K,3] fp32 or None (flipped faces are then not counted).
+        -> (faces' [F,3] int32: the corners' clusters, the smallest first, (-1, -1, -1) for a bad face; keep [F] uint8; state [3] int64
+        (device): degenerate, flipped, bad)"""
+        N, K, _ = self._cluster_args("mesh_cluster_remap", verts, faces, cluster, K, None)
+        self._chk_typed("mesh_cluster_remap", (new_verts, torch.float32))
+        if new_verts is not None and tuple(new_verts.shape) != (K, 3):
+            raise _lib.DmvsError(f"mesh_cluster_remap: new_verts must be [K,3] = [{K},3], got {tuple(new_verts.shape)}")
+        F = int(faces.shape[0])
+        out = torch.empty((F, 3), dtype=torch.int32, device=self.device)
+        keep = torch.empty((F,), dtype=torch.uint8, device=self.device)
+        state = torch.empty((3,), dtype=torch.int64, device=self.device)
+        self._call("dmvs_mesh_cluster_remap_i32", _ptr(verts), N, _ptr(faces), F, _ptr(cluster), K, _ptr(new_verts), _ptr(out), _ptr(keep), _ptr(state),
+                   int(blocks), self.stream())
+        return out, keep, state
+
 
 class TsdfVolume:
     """The caller-owned state of dmvs_tsdf_integrate_f32 (include/dmvs.h), made zeroed by Ops.tsdf_volume: dims (nx, ny, nz), origin (HOST,

@@ -901,6 +901,67 @@ int dmvs_mesh_face_tally_i64(const float* verts, int64_t N, const int32_t* faces
 int dmvs_mesh_sample_f32(const float* verts, int64_t N, const int32_t* faces, int64_t F, const int64_t* area_cum, int64_t a0, int64_t M,
                          float* points, int32_t* face_of, int32_t blocks, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Simplifying an extracted mesh (added under ABI 4, additive; diffmvs_amd/mesh_simplify.py): vertex clustering on a uniform lattice, each
+ * cluster's vertex at the minimum of its faces' summed plane quadrics, regularised towards the mean of its vertices.  Integer sums and
+ * IEEE fp64 in a fixed order without contraction: every output is bitwise independent of blocks, of timing and of the run.
+ *
+ * verts [N,3] fp32, rgb [N,3] uint8 or NULL, faces [F,3] int32, cluster [N] int32 (device): the caller's cluster of every vertex, a value
+ * outside [0, K) = "none" (diffmvs_amd/mesh_simplify.py: the rank of the vertex's lattice key among the occupied keys, -1 for a vertex with
+ * a non-finite coordinate).  origin [3] fp64 (HOST) and cell: the lattice.  blocks: workgroups of the grid-stride launches, 0 = the
+ * library's choice.  The LOCAL coordinate of a vertex p, per axis i:
+ *   t = (p_i - origin_i) / cell,  u_i = t - (floor(t) + 0.5)   in [-0.5, 0.5];  u_i = 0 where t is not finite (never with clusters made as above)
+ *
+ * dmvs_mesh_cluster_verts_i64: cnt [K] int32, pos_q [K,3] int64 and rgb_sum [K,3] int64 are zeroed here.  Per vertex with a cluster k:
+ *   cnt[k] += 1,  pos_q[k][i] += llrint(u_i * 2^32),  rgb_sum[k][i] += rgb[v][i] (rgb NULL: rgb_sum may be NULL and is not touched).
+ *
+ * dmvs_mesh_cluster_quadrics_i64: quad_q [K,10] int64 and state [2] int64 are zeroed here.  A face with an index outside [0, N) or a vertex
+ * without a cluster is BAD: state[0] += 1, nothing else.  Every other face, p0, p1, p2 widened to fp64, as dmvs_mesh_face_tally_i64 does:
+ *   a = p1 - p0,  b = p2 - p0,  c = (ay bz - az by, az bx - ax bz, ax by - ay bx),  l = sqrt((cx^2 + cy^2) + cz^2)
+ *   l zero or not finite: the face is FLAT, state[1] += 1, nothing else.   n = c / l,  w = fmin((0.5 * l) / (cell * cell), cap)
+ *   for each corner j whose cluster k differs from the clusters of the corners before it, with u the LOCAL coordinate of THAT corner:
+ *     d = -((nx ux + ny uy) + nz uz)      (the plane in the frame of the cell centre of the cluster it is added to)
+ *     quad_q[k][0 .. 9] += llrint(T * scale),  T = (w nx) nx, (w nx) ny, (w nx) nz, (w ny) ny, (w ny) nz, (w nz) nz,
+ *                                                  (w d) nx, (w d) ny, (w d) nz, (w d) d
+ *   |T| <= cap.  scale: a positive finite power of two; 0 <= cap < 2^62; 3 F cap scale < 2^62 (checked), so no sum overflows.  Integer atomics;
+ *   runs of neighbouring lanes of a wave that add to the same cluster are summed with shuffles first and go out as one lot (compiled with
+ *   -DDMVS_MESH_QUADRIC_PLAIN every lane issues its own): the order of integer sums is free.
+ *
+ * dmvs_mesh_cluster_place_f32: one lane per cluster k.  cells [K,3] int64: the cluster's lattice cell.  mode: DMVS_SIMPLIFY_QUADRIC or
+ * DMVS_SIMPLIFY_MEAN.  state [1] int64 is zeroed here.  out_rgb / rgb_sum may be NULL together.
+ *   A = [[q0 q1 q2] [q1 q3 q4] [q2 q4 q5]] / scale,  b = (q6, q7, q8) / scale   (exact: scale is a power of two)
+ *   m_i = ((double)pos_q[k][i] / 2^32) / (double)cnt[k]   (cnt 0: m = 0);  tr = (A00 + A11) + A22;  lam = reg * tr
+ *   M = A + lam I (diagonal only);  r_i = lam * m_i - b_i
+ *   c00 = M11 M22 - M12 M12,  c01 = M02 M12 - M01 M22,  c02 = M01 M12 - M02 M11,
+ *   c11 = M00 M22 - M02 M02,  c12 = M01 M02 - M00 M12,  c22 = M00 M11 - M01 M01,   det = (M00 c00 + M01 c01) + M02 c02
+ *   x0 = ((c00 r0 + c01 r1) + c02 r2) / det,  x1 = ((c01 r0 + c11 r1) + c12 r2) / det,  x2 = ((c02 r0 + c12 r1) + c22 r2) / det
+ *   good = tr > 0 and det > 0 and x finite and max |x_i| <= 1.   mode MEAN, or not good: x = m; mode QUADRIC, tr > 0 and not good: state[0] += 1.
+ *   out_verts[k][i] = (float)(origin_i + (((double)cells[k][i] + 0.5) + x_i) * cell)
+ *   out_rgb[k][i] = (2 rgb_sum[k][i] + cnt[k]) / (2 cnt[k]) in integers (cnt 0: 0).
+ *
+ * dmvs_mesh_cluster_remap_i32: out_faces [F,3] int32, keep [F] uint8; state [3] int64 is zeroed here.  A BAD face (as above): out_faces =
+ * (-1, -1, -1), keep = 0, state[2] += 1.  Every other face: its corners' clusters, rotated so that the smallest index comes first (the
+ * orientation stays); keep = 1 where the three differ, else 0 and state[0] += 1 (degenerate).  With new_verts [K,3] fp32 (may be NULL: nothing
+ * is counted), per kept face, corners in the face's INPUT order: c = the cross product above of the old positions, c' = the same formula on
+ * new_verts of the corners' clusters; state[1] += 1 where (cx c'x + cy c'y) + cz c'z < 0 (flipped).
+ *
+ * F = 0, N = 0 or K = 0: nothing but the zeroed outputs is touched (remap: every face is BAD when N or K is 0).  DMVS_EINVAL (before any
+ * launch): a negative size, N, F or K >= 2^31, NULL operands with work to do (origin and state always), an int32 / fp32 array not 4-byte
+ * or an int64 array not 8-byte aligned, blocks < 0, a cell or reg that is not positive and finite, a non-finite origin, a scale that is
+ * not a positive finite power of two, cap not in [0, 2^62), 3 F cap scale >= 2^62, an unknown mode. */
+#define DMVS_SIMPLIFY_QUADRIC 0
+#define DMVS_SIMPLIFY_MEAN 1
+int dmvs_mesh_cluster_verts_i64(const float* verts, const uint8_t* rgb, int64_t N, const int32_t* cluster, int64_t K, const double* origin,
+                                double cell, int32_t* cnt, int64_t* pos_q, int64_t* rgb_sum, int32_t blocks, void* stream);
+int dmvs_mesh_cluster_quadrics_i64(const float* verts, int64_t N, const int32_t* faces, int64_t F, const int32_t* cluster, int64_t K,
+                                   const double* origin, double cell, double scale, double cap, int64_t* quad_q, int64_t* state, int32_t blocks,
+                                   void* stream);
+int dmvs_mesh_cluster_place_f32(int64_t K, const int32_t* cnt, const int64_t* pos_q, const int64_t* rgb_sum, const int64_t* quad_q,
+                                const int64_t* cells, const double* origin, double cell, double scale, double reg, int32_t mode, float* out_verts,
+                                uint8_t* out_rgb, int64_t* state, void* stream);
+int dmvs_mesh_cluster_remap_i32(const float* verts, int64_t N, const int32_t* faces, int64_t F, const int32_t* cluster, int64_t K,
+                                const float* new_verts, int32_t* out_faces, uint8_t* keep, int64_t* state, int32_t blocks, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
