@@ -103,6 +103,7 @@ SIGNATURES = {
     "dmvs_cloud_nn_index_f32": [_P, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_double, _P, _F, _P, _P, _P, _P, _P],
     "dmvs_cloud_pair_moments_f64": [_P, C.c_int64, _P, _P, C.c_int64, _P, _P, _F, _P, _P, C.c_double, C.c_double, C.c_double, _I, _P, _P],
     "dmvs_cloud_crop_prism_f32": [_P, C.c_int64, _P, _P, _I, _I, C.c_double, C.c_double, _P, _P],
+    "dmvs_cloud_knn_f32": [_P, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_double, _P, _F, _P, _I, _P, _P, _P, _P, _P, _P],
     "dmvs_depth_stats_f32": [_P, _P, _P, C.c_int64, C.c_int64, _P, _I, C.c_double, C.c_double, C.c_double, C.c_double, _I, _P, _P],
     "dmvs_cloud_splat_zmin_f32": [_P, C.c_int64, _P, _P, C.c_int64, _I, _I, C.c_double, C.c_double, C.c_double, _I, _I, _P, _P, _P, _P],
     "dmvs_cloud_splat_sum_f32": [_P, C.c_int64, _P, _P, C.c_int64, _I, _I, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _I, _P, _P, _P, _P],
@@ -126,6 +127,7 @@ SIMPLIFY_QUADRIC, SIMPLIFY_MEAN = 0, 1      # dmvs.h: DMVS_SIMPLIFY_*
 VIEW_SELECT_MAX_IMAGES, VIEW_SELECT_MAX_LIST = 16384, 1 << 23      # dmvs.h: DMVS_VIEW_SELECT_MAX_IMAGES, DMVS_VIEW_SELECT_MAX_LIST
 CLOUD_MAX_RINGS, CLOUD_MAX_KEY_BITS, CLOUD_MAX_THRESHOLDS = 1024, 62, 16      # dmvs.h: DMVS_CLOUD_MAX_*
 CLOUD_MOMENTS, CLOUD_MAX_POLYGON = 20, 256      # dmvs.h: DMVS_CLOUD_MOMENTS, DMVS_CLOUD_MAX_POLYGON
+CLOUD_MAX_K = 32      # dmvs.h: DMVS_CLOUD_MAX_K
 DEPTH_MAX_THRESHOLDS, DEPTH_SLOTS = 8, 7      # dmvs.h: DMVS_DEPTH_MAX_THRESHOLDS, DMVS_DEPTH_SLOTS
 SPLAT_VIEW_CHUNK, SPLAT_VIEW_DOUBLES, SPLAT_SLOTS, SPLAT_MAX_RADIUS, SPLAT_NO_PRETEST = 8, 15, 4, 16, 0x1      # dmvs.h: DMVS_SPLAT_*
 NORMAL_MAX_RADIUS, NORMAL_CAM_DOUBLES, NORMAL_VIEW_CHUNK, NORMAL_SLOTS = 4, 27, 8, 4      # dmvs.h: DMVS_NORMAL_*

@@ -18,7 +18,12 @@ CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libdmvs_hip.so")
 PROBE_LIB = os.path.join(PKG, "libdmvs_probe.so")      # measurement probes (bench.py's untimed roofline legs); never loaded by the path
 PROBE_SOURCES = ["probe/getcost_probe.hip", "probe/random_line_gather.hip"]
-SOURCES = ["conv2d_k33.hip", "conv2d_k55.hip", "conv2d_k77.hip", "conv2d_k15.hip", "conv2d.hip", "stem.hip", "stem3.hip", "conv1_pair.hip", "fpn_tail.hip", "conv3d.hip", "warp_quad.hip", "warp_bwd.hip", "warp_bwd_win.hip", "warp_init_bwd_win.hip", "misc.hip", "mask_upsample.hip", "optim.hip", "norm.hip", "fusion.hip", "view_select.hip", "cloud_eval.hip", "cloud_register.hip", "depth_eval.hip", "cloud_render.hip", "depth_normals.hip", "tsdf.hip", "mesh_render.hip", "mesh_clean.hip", "mesh_simplify.hip"]
+SOURCES = ["conv2d_k33.hip", "conv2d_k55.hip", "conv2d_k77.hip", "conv2d_k15.hip", "conv2d.hip", "stem.hip", "stem3.hip", "conv1_pair.hip", "fpn_tail.hip", "conv3d.hip", "warp_quad.hip", "warp_bwd.hip", "warp_bwd_win.hip", "warp_init_bwd_win.hip", "misc.hip", "mask_upsample.hip", "optim.hip", "norm.hip", "fusion.hip", "view_select.hip", "cloud_eval.hip", "cloud_register.hip", "cloud_clean.hip", "depth_eval.hip", "cloud_render.hip", "depth_normals.hip", "tsdf.hip", "mesh_render.hip", "mesh_clean.hip", "mesh_simplify.hip"]
+# what every translation unit is compiled with
+FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
+         "-I", os.path.join(ROOT, "include"), "-I", CSRC,
+         "-munsafe-fp-atomics",          # hardware global_atomic_add_f32/f64 (gradient scatter, GroupNorm stats)
+         "-Wall", "-Wno-unused-function"]
 
 
 def _deps():
@@ -41,10 +46,7 @@ def build_hip(force: bool = False, save_temps: bool = False, verbose: bool = Tru
     import time
     t_start = time.time()          # the libraries are stamped with the START of the build: a source edited while it ran makes them stale
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
-             "-I", os.path.join(ROOT, "include"), "-I", CSRC,
-             "-munsafe-fp-atomics",          # hardware global_atomic_add_f32/f64 (gradient scatter, GroupNorm stats)
-             "-Wall", "-Wno-unused-function"]
+    flags = list(FLAGS)
     objdir = os.path.join(ROOT, "build", "temps" if save_temps else "obj")
     os.makedirs(objdir, exist_ok=True)
     if save_temps:

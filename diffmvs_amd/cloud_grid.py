@@ -49,14 +49,15 @@ def key(c: torch.Tensor, dims) -> torch.Tensor:
 
 def build_grid(target: torch.Tensor, cell: float) -> dict:
     """sort `target` [M,3] fp32 into a uniform grid of cell side `cell` whose origin is the cloud's minimum corner.
-    -> {target (sorted), keys [C], start [C+1], origin, dims, cell}: the operands of Ops.cloud_nn_dist"""
+    -> {target (sorted), keys [C], start [C+1], origin, dims, cell}: the operands of Ops.cloud_nn_dist; and order [M] int64, the input
+    position of every sorted target (target_sorted = target[order]: what a self search scatters its results back with)"""
     if not (cell > 0 and math.isfinite(cell)):
         raise ValueError(f"cell size must be positive and finite, got {cell}")
     dev = target.device
     if target.shape[0] == 0:
         z = torch.zeros(0, dtype=torch.int64, device=dev)
         return {"target": target.reshape(0, 3).contiguous(), "keys": z, "start": torch.zeros(1, dtype=torch.int64, device=dev),
-                "origin": (0.0, 0.0, 0.0), "dims": (1, 1, 1), "cell": float(cell)}
+                "origin": (0.0, 0.0, 0.0), "dims": (1, 1, 1), "cell": float(cell), "order": z}
     if not bool(torch.isfinite(target).all()):
         raise ValueError("the target cloud holds non-finite coordinates")
     lo = target.min(0).values.double()
@@ -69,7 +70,8 @@ def build_grid(target: torch.Tensor, cell: float) -> dict:
     keys, counts = torch.unique_consecutive(skey, return_counts=True)
     start = torch.zeros(keys.numel() + 1, dtype=torch.int64, device=dev)
     torch.cumsum(counts, 0, out=start[1:])
-    return {"target": target[order].contiguous(), "keys": keys, "start": start, "origin": origin, "dims": dims, "cell": float(cell)}
+    return {"target": target[order].contiguous(), "keys": keys, "start": start, "origin": origin, "dims": dims, "cell": float(cell),
+            "order": order}
 
 
 def order_by_grid(points: torch.Tensor, grid: dict):

@@ -1,7 +1,8 @@
 // The grid walk of the point-cloud kernels, shared by dmvs_cloud_nn_dist_f32 (cloud_eval.hip) and dmvs_cloud_nn_index_f32
 // (cloud_register.hip); the walk itself is described at the top of cloud_eval.hip.  INDEX = true also tracks WHICH target is the
 // nearest (one more register and a select per target tested); with INDEX = false that member is never read and the walk compiles
-// to what it was before the index search existed.  Also here: what the fixed-point reductions of both files share (cloud_block_sum
+// to what it was before the index search existed.  The walk is written once over a collector, so dmvs_cloud_knn_f32 (cloud_clean.hip)
+// runs the same code with a k-best list in place of the single best.  Also here: what the fixed-point reductions of both files share (cloud_block_sum
 // and the host-side shaping of its launches).
 #pragma once
 #include <math.h>
@@ -58,48 +59,58 @@ struct CloudQuery {
     float qx, qy, qz;
     double tx, ty, tz;          // position inside the (clamped) own cell, in cells
     int cx, cy, cz;
-    float best2;
-    int best_i;                 // INDEX: the target that gave best2 (-1: none yet)
     int points;                 // targets tested (the optional work output)
 };
 
+// What a search keeps of the targets it tests is its COLLECTOR: bound() is the squared distance a target has to beat (the walk prunes
+// against it), take(d2, p) is handed every tested target p with its squared distance.  CloudNearest is the collector of the two nearest
+// searches; CloudKBest (cloud_clean.hip) keeps the k smallest.
 template <bool INDEX>
-__device__ __forceinline__ void cloud_scan_cell(CloudQuery& q, const CloudGrid& g, const float* __restrict__ target, long c) {
+struct CloudNearest {
+    float best2;
+    int best_i;                 // INDEX: the target that gave best2 (-1: none yet)
+    __device__ __forceinline__ float bound() const { return best2; }
+    __device__ __forceinline__ void take(float d2, long p) {
+        if (INDEX) best_i = d2 < best2 ? (int)p : best_i;      // (strict: the first of exactly equidistant targets in walk order stays)
+        best2 = d2 < best2 ? d2 : best2;
+    }
+};
+
+template <class COL>
+__device__ __forceinline__ void cloud_scan_cell(CloudQuery& q, COL& col, const CloudGrid& g, const float* __restrict__ target, long c) {
 #pragma clang fp contract(off)
     const long p0 = g.start[c], p1 = g.start[c + 1];
     for (long p = p0; p < p1; ++p) {
         const float dx = q.qx - target[3 * p], dy = q.qy - target[3 * p + 1], dz = q.qz - target[3 * p + 2];
-        const float d2 = (dx * dx + dy * dy) + dz * dz;
-        if (INDEX) q.best_i = d2 < q.best2 ? (int)p : q.best_i;      // (strict: the first of exactly equidistant targets in walk order stays)
-        q.best2 = d2 < q.best2 ? d2 : q.best2;
+        col.take((dx * dx + dy * dy) + dz * dz, p);
     }
     q.points += (int)(p1 - p0);
 }
 
 // one occupied row (y, z): its cells outward from the query's x; g2yz = squared gap of the row (length units)
-template <bool INDEX>
-__device__ __forceinline__ void cloud_visit_row(CloudQuery& q, const CloudGrid& g, const float* __restrict__ target, int y, int z, float g2yz) {
+template <class COL>
+__device__ __forceinline__ void cloud_visit_row(CloudQuery& q, COL& col, const CloudGrid& g, const float* __restrict__ target, int y, int z, float g2yz) {
     const int64_t row = ((int64_t)z << g.by) | y, base = row << g.bx;
     const long cm = cloud_lower_bound(g.keys, 0, g.C, base | q.cx);
     for (long c = cm; c < g.C; ++c) {                      // x >= cx
         const int64_t k = g.keys[c];
         if ((k >> g.bx) != row) break;
         const float gx = (float)(cloud_gap((int)(k - base) - q.cx, q.tx) * g.h);
-        if (gx * gx + g2yz >= q.best2 * kPruneMargin) break;
-        cloud_scan_cell<INDEX>(q, g, target, c);
+        if (gx * gx + g2yz >= col.bound() * kPruneMargin) break;
+        cloud_scan_cell(q, col, g, target, c);
     }
     for (long c = cm - 1; c >= 0; --c) {                   // x < cx
         const int64_t k = g.keys[c];
         if ((k >> g.bx) != row) break;
         const float gx = (float)(cloud_gap((int)(k - base) - q.cx, q.tx) * g.h);
-        if (gx * gx + g2yz >= q.best2 * kPruneMargin) break;
-        cloud_scan_cell<INDEX>(q, g, target, c);
+        if (gx * gx + g2yz >= col.bound() * kPruneMargin) break;
+        cloud_scan_cell(q, col, g, target, c);
     }
 }
 
 // one slab z: its occupied rows outward from the query's y
-template <bool INDEX>
-__device__ __forceinline__ void cloud_visit_slab(CloudQuery& q, const CloudGrid& g, const float* __restrict__ target, int z, float g2z) {
+template <class COL>
+__device__ __forceinline__ void cloud_visit_slab(CloudQuery& q, COL& col, const CloudGrid& g, const float* __restrict__ target, int z, float g2z) {
     const int sh = g.bx + g.by;
     const int64_t ymask = ((int64_t)1 << g.by) - 1;
     for (int y = q.cy; y < g.ny;) {                        // rows >= cy: the first occupied row at or after y
@@ -110,8 +121,8 @@ __device__ __forceinline__ void cloud_visit_slab(CloudQuery& q, const CloudGrid&
         const int yo = (int)((k >> g.bx) & ymask);
         const float gy = (float)(cloud_gap(yo - q.cy, q.ty) * g.h);
         const float g2 = gy * gy + g2z;
-        if (g2 >= q.best2 * kPruneMargin) break;
-        cloud_visit_row<INDEX>(q, g, target, yo, z, g2);
+        if (g2 >= col.bound() * kPruneMargin) break;
+        cloud_visit_row(q, col, g, target, yo, z, g2);
         y = yo + 1;
     }
     for (int y = q.cy - 1; y >= 0;) {                      // rows < cy: the last occupied row at or before y
@@ -122,8 +133,8 @@ __device__ __forceinline__ void cloud_visit_slab(CloudQuery& q, const CloudGrid&
         const int yo = (int)((k >> g.bx) & ymask);
         const float gy = (float)(cloud_gap(yo - q.cy, q.ty) * g.h);
         const float g2 = gy * gy + g2z;
-        if (g2 >= q.best2 * kPruneMargin) break;
-        cloud_visit_row<INDEX>(q, g, target, yo, z, g2);
+        if (g2 >= col.bound() * kPruneMargin) break;
+        cloud_visit_row(q, col, g, target, yo, z, g2);
         y = yo - 1;
     }
 }
@@ -131,6 +142,37 @@ __device__ __forceinline__ void cloud_visit_slab(CloudQuery& q, const CloudGrid&
 __device__ __forceinline__ int cloud_clamp_cell(double u, int n) {
     const double f = floor(u);
     return f < 0.0 ? 0 : (f > (double)(n - 1) ? n - 1 : (int)f);      // (u is finite: checked by the caller)
+}
+
+// the walk of one query (q.qx, q.qy, q.qz set by the caller) into `col`: rings of slabs outward in z until no unseen slab can beat the
+// collector's bound.  -> rings walked (0: an empty grid or a non-finite query, nothing tested); q.points counts the targets tested
+template <class COL>
+__device__ __forceinline__ int cloud_walk(CloudQuery& q, COL& col, const CloudGrid& g, const float* __restrict__ target) {
+    const double ux = ((double)q.qx - g.ox) / g.h, uy = ((double)q.qy - g.oy) / g.h, uz = ((double)q.qz - g.oz) / g.h;
+    int rings = 0;
+    q.points = 0;
+    if (g.C > 0 && isfinite(ux) && isfinite(uy) && isfinite(uz)) {
+        q.cx = cloud_clamp_cell(ux, g.nx), q.cy = cloud_clamp_cell(uy, g.ny), q.cz = cloud_clamp_cell(uz, g.nz);
+        q.tx = ux - q.cx, q.ty = uy - q.cy, q.tz = uz - q.cz;
+        bool up = true, down = true;
+        for (int r = 0; up || down; ++r) {
+            rings = r + 1;
+            if (up) {
+                const int z = q.cz + r;
+                const float gz = (float)(cloud_gap(r, q.tz) * g.h);
+                if (z >= g.nz || gz * gz >= col.bound() * kPruneMargin) up = false;
+                else cloud_visit_slab(q, col, g, target, z, gz * gz);
+            }
+            if (r == 0) continue;
+            if (down) {
+                const int z = q.cz - r;
+                const float gz = (float)(cloud_gap(-r, q.tz) * g.h);
+                if (z < 0 || gz * gz >= col.bound() * kPruneMargin) down = false;
+                else cloud_visit_slab(q, col, g, target, z, gz * gz);
+            }
+        }
+    }
+    return rings;
 }
 
 // the search of one query: moves it (T), walks the grid, writes dist (may be NULL with INDEX) / index (INDEX only) / work (may be NULL)
@@ -143,36 +185,14 @@ cloud_nn_kernel(const float* __restrict__ query, long Q, const float* __restrict
     CloudQuery q;
     q.qx = query[3 * i], q.qy = query[3 * i + 1], q.qz = query[3 * i + 2];
     if (INDEX) cloud_move(T, q.qx, q.qy, q.qz);
-    const double ux = ((double)q.qx - g.ox) / g.h, uy = ((double)q.qy - g.oy) / g.h, uz = ((double)q.qz - g.oz) / g.h;
-    int rings = 0;
-    q.points = 0;
-    q.best_i = -1;
-    q.best2 = max_dist * max_dist;
-    if (g.C > 0 && isfinite(ux) && isfinite(uy) && isfinite(uz)) {
-        q.cx = cloud_clamp_cell(ux, g.nx), q.cy = cloud_clamp_cell(uy, g.ny), q.cz = cloud_clamp_cell(uz, g.nz);
-        q.tx = ux - q.cx, q.ty = uy - q.cy, q.tz = uz - q.cz;
-        bool up = true, down = true;
-        for (int r = 0; up || down; ++r) {
-            rings = r + 1;
-            if (up) {
-                const int z = q.cz + r;
-                const float gz = (float)(cloud_gap(r, q.tz) * g.h);
-                if (z >= g.nz || gz * gz >= q.best2 * kPruneMargin) up = false;
-                else cloud_visit_slab<INDEX>(q, g, target, z, gz * gz);
-            }
-            if (r == 0) continue;
-            if (down) {
-                const int z = q.cz - r;
-                const float gz = (float)(cloud_gap(-r, q.tz) * g.h);
-                if (z < 0 || gz * gz >= q.best2 * kPruneMargin) down = false;
-                else cloud_visit_slab<INDEX>(q, g, target, z, gz * gz);
-            }
-        }
-    }
-    const float d = q.best2 < max_dist * max_dist ? fminf(sqrtf(q.best2), max_dist) : max_dist;
+    CloudNearest<INDEX> col;
+    col.best_i = -1;
+    col.best2 = max_dist * max_dist;
+    const int rings = cloud_walk(q, col, g, target);
+    const float d = col.best2 < max_dist * max_dist ? fminf(sqrtf(col.best2), max_dist) : max_dist;
     if (INDEX) {
         if (dist) dist[i] = d;
-        index[i] = d < max_dist ? q.best_i : -1;      // -1 exactly where the distance is the clamp
+        index[i] = d < max_dist ? col.best_i : -1;      // -1 exactly where the distance is the clamp
     } else {
         dist[i] = d;
     }

@@ -134,6 +134,14 @@ def main(argv=None, device=None):
     ap.add_argument("--normal_min_pts", type=int, default=5, help="--normals: pixels with fewer neighbours in the fit get no normal")
     ap.add_argument("--max_view_angle", type=float, default=None, help="with --filter (implies --normals): leave points out of the cloud that have no normal or "
                     "are seen at more than this many degrees off their normal")
+    ap.add_argument("--cloud_knn", type=int, default=None, metavar="K", help="with --filter: statistical outlier removal on the fused cloud before it is written "
+                    "(diffmvs_amd.cloud_clean): points whose mean distance to their K nearest neighbours exceeds the cloud's mean + --cloud_std_ratio "
+                    "deviations go; adds cloud_clean[scene] to the result")
+    ap.add_argument("--cloud_std_ratio", type=float, default=2.0, metavar="S", help="--cloud_knn: deviations above the mean that are kept")
+    ap.add_argument("--cloud_min_neighbours", type=int, default=None, metavar="N", help="with --filter and --cloud_radius: keep fused points with at least N "
+                    "others closer than the radius")
+    ap.add_argument("--cloud_radius", type=float, default=None, metavar="R", help="--cloud_min_neighbours: the radius, world units")
+    ap.add_argument("--cloud_voxel", type=float, default=None, metavar="V", help="with --filter: thin the fused cloud to one point per voxel of this side first")
     ap.add_argument("--mesh", action="store_true", help="with --filter: also write the averaged depth maps (depth_fused/) and mesh every scene to <scene>/mesh.ply "
                     "(TSDF fusion and surface nets on the GPU: diffmvs_amd.mesh); adds mesh[scene] to the result")
     ap.add_argument("--mesh_voxel", type=float, default=None, help="--mesh: voxel side in world units")
@@ -209,8 +217,16 @@ def main(argv=None, device=None):
                           max_view_angle=a.max_view_angle, stats=res.setdefault("normals", {}).setdefault(scene, {}))
             if a.mesh:
                 kw.update(write_fused=True)
+            tidy = {k: v for k, v in (("knn", a.cloud_knn), ("min_neighbours", a.cloud_min_neighbours), ("radius", a.cloud_radius),
+                                      ("voxel", a.cloud_voxel)) if v is not None}
+            if tidy:
+                if a.cloud_knn is not None:
+                    tidy["std_ratio"] = a.cloud_std_ratio
+                kw.update(clean=tidy, stats=kw.get("stats", {}))
             n = fusion.filter_depth(os.path.join(a.testpath, scene), os.path.join(a.outdir, scene), method=a.method, device=device, **kw)
             res.setdefault("fused_points", {})[scene] = n
+            if tidy:
+                res.setdefault("cloud_clean", {})[scene] = kw["stats"].pop("cloud_clean")
             res.setdefault("ply", {})[scene] = kw["plyfilename"]
             if a.mesh:
                 from . import mesh

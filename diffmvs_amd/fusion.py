@@ -148,7 +148,7 @@ def view_normals(ops: Ops, depth: np.ndarray, mask: np.ndarray, K, E, radius=2, 
 def filter_depth(pair_folder, out_folder, plyfilename, geo_mask_thres=3, geo_pixel_thres=1.0, geo_depth_thres=0.01,
                  photo_thres=(0.3, 0.5, 0.5), method="casdiffmvs", dataset="dtu", scan=None, device="cuda:0", ops: Ops | None = None,
                  normals=False, normal_radius=2, normal_jump=0.02, normal_min_pts=5, max_view_angle=None, stats: dict | None = None,
-                 write_fused=False) -> int:
+                 write_fused=False, clean: dict | None = None) -> int:
     """filter.py:95-227 (dataset != 'tank') / :261-441 (dataset == 'tank': `scan` picks the dynamic parameters) over one
     scene's output tree; writes mask/*.png and the fused point cloud.  -> number of fused points.
     normals: the PLY also carries nx ny nz, the oriented normal of every point from view_normals() on the view's averaged depth (fp32)
@@ -157,7 +157,10 @@ def filter_depth(pair_folder, out_folder, plyfilename, geo_mask_thres=3, geo_pix
     the reference's.  stats: a dict that receives {"slots": the four slot totals of include/dmvs.h over all views, "no_normal": written
     points that carry (0, 0, 0), "dropped": points max_view_angle left out} when normals are on.  With the defaults every output is
     what it was without these options.
-    write_fused: also writes the averaged depth of every reference view as depth_fused/%08d.pfm (fp32), what diffmvs_amd.mesh integrates."""
+    write_fused: also writes the averaged depth of every reference view as depth_fused/%08d.pfm (fp32), what diffmvs_amd.mesh integrates.
+    clean: keyword arguments of cloud_clean.clean (voxel, min_neighbours / radius, knn / std_ratio / max_dist, cell): the concatenated cloud,
+    its colours and normals go through it just before they are written; the cleaned count is returned and `stats` receives
+    {"cloud_clean": its info}.  The masks stay the reference's."""
     from PIL import Image
     ops = ops or Ops.for_device(device)
     if os.path.dirname(plyfilename):
@@ -205,8 +208,13 @@ def filter_depth(pair_folder, out_folder, plyfilename, geo_mask_thres=3, geo_pix
             nrms.append(nrm[:, :3])
         verts.append(pts)
         cols.append(col)
-    xyz, rgb = np.concatenate(verts, 0), np.concatenate(cols, 0)
-    IO.write_ply(plyfilename, xyz.astype(np.float32), rgb, np.concatenate(nrms, 0) if want_normals else None)
+    xyz, rgb, nrm = np.concatenate(verts, 0).astype(np.float32), np.concatenate(cols, 0), np.concatenate(nrms, 0) if want_normals else None
+    if clean:
+        from . import cloud_clean
+        xyz, rgb, nrm, _, info = cloud_clean.clean(ops, xyz, rgb, nrm, **clean)
+        if stats is not None:
+            stats["cloud_clean"] = info
+    IO.write_ply(plyfilename, xyz, rgb, nrm)
     if want_normals and stats is not None:
         stats.update(slots=[int(v) for v in slots], no_normal=no_normal, dropped=dropped)
     return int(xyz.shape[0])

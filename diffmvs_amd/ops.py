@@ -960,6 +960,33 @@ class Ops:
                    float(axis_min), float(axis_max), _ptr(out), self.stream())
         return out
 
+    # ------------------------------------------------------------------ point-cloud cleaning (diffmvs_amd/cloud_clean.py)
+    def cloud_knn(self, query, target, cell_keys, cell_start, origin, h, dims, max_dist, k, self_index=None, d2=False, work=False):
+        """dmvs_cloud_knn_f32: the k nearest targets of every query closer than max_dist, over the grid operands of cloud_nn_dist
+        (include/dmvs.h).  self_index: None or [Q] int32, the sorted-target position query i must not match (-1: none).
+        -> {"mean" [Q] fp32, "kth" [Q] fp32, "found" [Q] int32[, "d2" [Q,k] fp32 ascending, padded with max_dist^2][, "work" [Q,2] int32]}."""
+        self._chk_typed("cloud_knn", (query, torch.float32), (target, torch.float32), (cell_keys, torch.int64), (cell_start, torch.int64),
+                        (self_index, torch.int32))
+        Q, M, Cn, k = int(query.shape[0]), int(target.shape[0]), int(cell_keys.numel()), int(k)
+        if query.dim() != 2 or query.shape[1] != 3 or target.dim() != 2 or target.shape[1] != 3:
+            raise _lib.DmvsError("cloud_knn: query and target must be [N,3]")
+        if cell_start.numel() != Cn + 1 or Cn > M or (M > 0 and Cn < 1):
+            raise _lib.DmvsError("cloud_knn: cell_start must have one entry more than cell_keys, and every target a cell")
+        if not 1 <= k <= _lib.CLOUD_MAX_K:
+            raise _lib.DmvsError(f"cloud_knn: k = {k}; 1..{_lib.CLOUD_MAX_K} are supported")
+        if self_index is not None and self_index.numel() != Q:
+            raise _lib.DmvsError("cloud_knn: self_index must have one entry per query")
+        out = {"mean": self.empty(Q), "kth": self.empty(Q), "found": torch.empty(Q, dtype=torch.int32, device=self.device)}
+        if d2:
+            out["d2"] = self.empty(Q, k)
+        if work:
+            out["work"] = torch.empty(Q, 2, dtype=torch.int32, device=self.device)
+        self._call("dmvs_cloud_knn_f32", _ptr(query), Q, _ptr(target), M, _ptr(cell_keys), _ptr(cell_start), Cn,
+                   (C.c_double * 3)(*[float(v) for v in origin]), float(h), (C.c_int32 * 3)(*[int(v) for v in dims]), float(max_dist),
+                   _ptr(self_index), k, _ptr(out.get("d2")), _ptr(out["kth"]), _ptr(out["mean"]), _ptr(out["found"]), _ptr(out.get("work")),
+                   self.stream())
+        return out
+
     # ------------------------------------------------------------------ depth-map scoring (diffmvs_amd/depth_eval.py)
     def depth_stats(self, est, gt, mask, thresholds, big, scale, band=None, blocks=0):
         """dmvs_depth_stats_f32 -> [B, 7 + T] int64 on the device, one row per batch item: masked pixels, scored pixels, pixels left out

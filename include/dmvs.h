@@ -616,6 +616,29 @@ int dmvs_cloud_crop_prism_f32(const float* points, int64_t N, const double* tran
                               int32_t axis, double axis_min, double axis_max, uint8_t* inside, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Point-cloud cleaning (added under ABI 4, additive; diffmvs_amd/cloud_clean.py builds the radius and the statistical outlier filters on it).
+ *
+ * dmvs_cloud_knn_f32: the k nearest targets of every query, over the grid operands and the walk of dmvs_cloud_nn_dist_f32.
+ *   self_index: NULL or [Q] int32, the position in the SORTED target array that query i must not match (the query itself in a self
+ *   search); -1 = none.  1 <= k <= DMVS_CLOUD_MAX_K.
+ *   The candidates of query i are the targets p != self_index[i] with d2 = (dx dx + dy dy) + dz dz < md2, the fp32 squared distance of
+ *   the nearest searches (same operation order, no contraction), md2 = max_dist * max_dist in fp32.  A duplicate of the query at
+ *   another position is a candidate with d2 = 0.
+ *   found [Q] int32 = min(k, number of candidates).
+ *   d2_out: NULL or [Q,k] fp32 = the found[i] smallest candidate d2 in ascending order, padded with md2.  Ties at the k-th place have
+ *     equal values, so this multiset -- and everything below -- is the same bits for any cell size and walk order.
+ *   kth [Q] fp32 = sqrtf(d2_out[i, k-1]) where found[i] == k, else max_dist: "at least k others closer than r" is found == k at max_dist = r.
+ *   mean [Q] fp32 = (float)(S / (double)found[i]), S = the sum of sqrt((double)d2_j) over the found entries in ascending order, fp64
+ *     without contraction; max_dist where found[i] == 0.
+ *   A non-finite query finds nothing (found = 0), as in the nearest searches.  work as in dmvs_cloud_nn_dist_f32.
+ *   DMVS_EINVAL: as dmvs_cloud_nn_index_f32 (d2_out and self_index may be NULL; kth, mean and found may not), k outside [1, DMVS_CLOUD_MAX_K]. */
+#define DMVS_CLOUD_MAX_K 32
+int dmvs_cloud_knn_f32(const float* query, int64_t Q, const float* target, int64_t M, const int64_t* cell_keys,
+                       const int64_t* cell_start, int64_t C, const double* origin, double h, const int32_t* dims,
+                       float max_dist, const int32_t* self_index, int32_t k, float* d2_out, float* kth, float* mean,
+                       int32_t* found, int32_t* work, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Depth-map scoring (added under ABI 4, additive): the per-pixel errors of utils.py:150-187 (AbsDepthError_metrics) and the "DTU abs-rel"
  * of BASELINE.json as integer and fixed-point sums per batch item (diffmvs_amd/depth_eval.py turns the rows into the metrics).
  *
